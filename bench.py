@@ -22,7 +22,14 @@ shared-memory transport instead (ranks sharing one GPU). Scaling "strong": total
 data path (scaling "weak").
 value = all k-mers processed / max-over-ranks step time.
 
+A plain run sets up, warms up, times the steps and prints the result line. --full adds the
+measurements beside it, each a run of its own: the FASTQ-inclusive span through the mcaat CLI
+(`e2e`, `span`), relevant-read mapping (`post_path`), FASTQ ingest (`fastq_ingest`) and the CPU
+baseline (`cpu_baseline`); without it those fields are null. --dump-outputs DIR writes what the
+last timed step returned (dump_arrays) as DIR/<name>.npy.
+
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|tiny] [--mode shard|replicas]
+                       [--full] [--dump-outputs DIR]
        N>1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 """
 from __future__ import annotations
@@ -350,6 +357,44 @@ def measure_ingest(ctx, spec, n_reads: int) -> dict:
                 "and GPU parse",
     }
 
+
+def dump_arrays(D: int, res) -> dict:
+    """What one step hands its caller (the SDBG's edge count and CycleFinder's results copied to
+    the host), as flat float64 arrays: entry i starts at cycle_starts[i] and holds the cycles
+    cycle_entry_offsets[i]..[i+1]; cycle j is cycle_nodes[cycle_offsets[j]:cycle_offsets[j+1]].
+    Node ids are edge indices (< D < 2^53), so float64 holds them exactly."""
+    starts = np.array([s for s, _ in res.entries], dtype=np.uint64)
+    per_entry = [np.diff(np.asarray(offs, dtype=np.int64)) for _, (_, offs) in res.entries]
+    n_cyc = np.array([len(x) for x in per_entry], dtype=np.int64)
+    lens = np.concatenate(per_entry) if per_entry else np.zeros(0, np.int64)
+    nodes = np.concatenate([flat for _, (flat, _) in res.entries]) if res.entries else np.zeros(0, np.uint64)
+    out = {
+        "sdbg_edges": np.array([D], dtype=np.uint64),
+        "cycle_starts": starts,
+        "cycle_entry_offsets": np.concatenate([[0], np.cumsum(n_cyc)]),
+        "cycle_offsets": np.concatenate([[0], np.cumsum(lens)]),
+        "cycle_nodes": nodes,
+        "cf_stats": np.array(res.stats, dtype=np.uint64),
+        "start_candidates": np.asarray(res.candidates, dtype=np.uint64),
+        "candidate_buckets": np.asarray(res.buckets, dtype=np.int64),
+    }
+    for name, a in out.items():
+        if a.size and int(a.max()) >= 1 << 53:
+            raise ValueError(f"{name} holds a value float64 cannot represent")
+    return {name: a.astype(np.float64) for name, a in out.items()}
+
+
+def dump_outputs(folder: str, arrays: dict, limit: int = 64 << 20) -> None:
+    """DIR/<name>.npy per array; a fixed, seeded sample of the largest ones past `limit` bytes in all."""
+    os.makedirs(folder, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > limit and a.nbytes > limit // (2 * len(arrays)):
+            keep = limit // (2 * len(arrays)) // a.itemsize
+            a = a[np.sort(np.random.default_rng(12345).choice(a.size, size=keep, replace=False))]
+        np.save(os.path.join(folder, name + ".npy"), a)
+
+
 # per-stage collective counters of the sharded path (kstats "xr_<stage>" / "xq_<stage>")
 XR_STAGES = ("build", "tips_filter", "peel", "recount", "candidates", "dls", "find_cycle")
 
@@ -362,17 +407,24 @@ def main() -> int:
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
     ap.add_argument("--reads", type=int, default=0, help="override n_reads")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0: OMP_NUM_THREADS or the affinity set")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beside the headline figure: the FASTQ-inclusive span (e2e), "
+                         "relevant-read mapping (post_path), FASTQ ingest and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-e2e", action="store_true",
-                    help="skip the FASTQ-inclusive span (the workload as FASTQ in /dev/shm through the mcaat CLI)")
-    ap.add_argument("--no-post", action="store_true", help="skip the untimed relevant-read mapping measurement")
+                    help="with --full: skip the FASTQ-inclusive span (the workload as FASTQ in /dev/shm through the mcaat CLI)")
+    ap.add_argument("--no-post", action="store_true", help="with --full: skip the untimed relevant-read mapping measurement")
     ap.add_argument("--ingest-reads", type=int, default=2_000_000,
-                    help="untimed FASTQ ingest measurement on a file of this many reads (0: skip)")
+                    help="with --full: untimed FASTQ ingest measurement on a file of this many reads (0: skip)")
     ap.add_argument("--mode", default="shard", choices=["shard", "replicas"],
                     help="N>1: one dataset hash-range sharded over the ranks, or one dataset per rank")
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU-only rehearsal of the control flow (ranks, barrier, max-reduce, JSON); no GPU work")
     args = ap.parse_args()
+    if args.dump_outputs and args.steps < 1:
+        ap.error("--dump-outputs needs at least one timed step")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -428,7 +480,7 @@ def main() -> int:
     # used: VRAM released by a process is scrubbed by the driver, and a CLI started right after
     # the bench freed ~200 GB would wait for that inside its span.
     e2e = None
-    if rank == 0 and world == 1 and not args.dry_run and not args.no_e2e:
+    if rank == 0 and world == 1 and args.full and not args.dry_run and not args.no_e2e:
         e2e = run_e2e(ctx, reads, cfg, spec, n_occ(spec, k))
 
     def step():
@@ -494,7 +546,9 @@ def main() -> int:
     # after the timed region (not part of `value`): the next step of the reference's main,
     # relevant-read mapping (reads.cpp:88-130) on the GPU over the reads still in HBM
     post = None
-    if rank == 0 and not args.dry_run and not sharded and not args.no_post:
+    if rank == 0 and args.dump_outputs and not args.dry_run:  # rank 0's results (shard mode: every rank's)
+        dump_outputs(args.dump_outputs, dump_arrays(D, res))
+    if rank == 0 and args.full and not args.dry_run and not sharded and not args.no_post:
         g = M.Graph.build(ctx, reads, k)
         r2 = g.cycle_finder(prm)
         nodes = np.array(sorted({x for _, cyc in r2.entries for c in cyc for x in c}), dtype=np.uint64)
@@ -516,7 +570,7 @@ def main() -> int:
         }
         g.free()
     ingest = None
-    if rank == 0 and world == 1 and not args.dry_run and args.ingest_reads > 0:
+    if rank == 0 and world == 1 and args.full and not args.dry_run and args.ingest_reads > 0:
         ingest = measure_ingest(ctx, spec, args.ingest_reads)
     kmers_rank = count * max(0, spec.read_len - k)
     kmers_total = n_occ(spec, k) if sharded else kmers_rank * world
@@ -601,7 +655,7 @@ def main() -> int:
                         f"(profiles/traffic_{args.config}.json; FETCH doubled only for wide coalesced "
                         "stream reads: corrected, and as counted: raw)",
             }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.dry_run:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and not args.dry_run:
         try:
             out["cpu_baseline"] = cpu_baseline(ctx, cfg, args.cpu_threads or host_threads())
         except Exception as e:  # reported, never fatal for the GPU number

@@ -112,6 +112,72 @@ def test_bench_two_ranks_gloo_dry_run(mode, port):
         assert d["config"]["reads_total"] == 10_000
 
 
+def test_bench_dump_arrays_layout_and_sample(tmp_path):
+    """bench.py --dump-outputs: the flat float64 layout of one step's results, and the fixed
+    sample that keeps a large dump within its size limit."""
+    import bench
+
+    u64 = lambda *x: np.array(x, dtype=np.uint64)  # noqa: E731
+    res = M.CycleResult(entries=[(7, (u64(7, 8, 9, 7, 3), u64(0, 3, 5))), (2, (u64(2, 4), u64(0, 2)))],
+                        stats=[1, 2, 3, 4, 5, 3, 0, 1], candidates=u64(2, 7), buckets=np.array([0, 1], np.int32))
+    a = bench.dump_arrays(1 << 40, res)
+    assert all(v.dtype == np.float64 and v.ndim == 1 for v in a.values())
+    assert a["sdbg_edges"].tolist() == [float(1 << 40)]
+    assert a["cycle_starts"].tolist() == [7, 2]
+    assert a["cycle_entry_offsets"].tolist() == [0, 2, 3]
+    assert a["cycle_offsets"].tolist() == [0, 3, 5, 7]
+    assert a["cycle_nodes"].tolist() == [7, 8, 9, 7, 3, 2, 4]
+    assert a["cf_stats"].tolist() == res.stats
+    assert a["start_candidates"].tolist() == [2, 7] and a["candidate_buckets"].tolist() == [0, 1]
+    empty = bench.dump_arrays(0, M.CycleResult(stats=[0] * 8, candidates=u64(), buckets=np.zeros(0, np.int32)))
+    assert empty["cycle_nodes"].size == 0 and empty["cycle_offsets"].tolist() == [0]
+    res.entries[0] = (1 << 53, res.entries[0][1])  # float64 would round it
+    with pytest.raises(ValueError):
+        bench.dump_arrays(1, res)
+
+    big = {"small": np.arange(10, dtype=np.float64), "big": np.arange(5000, dtype=np.float64)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), big, limit=8000)
+    got = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in big}
+    assert np.array_equal(got["small"], big["small"])
+    assert 0 < got["big"].size < 5000 and sum(v.nbytes for v in got.values()) <= 8000
+    assert np.all(np.diff(got["big"]) > 0)  # a subset of the array, in its order
+    assert np.array_equal(got["big"], np.load(tmp_path / "b" / "big.npy"))  # the same sample every run
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_the_step_results(gpu_ctx, tmp_path):
+    """A plain bench run times the steps and leaves the --full measurements out of its line;
+    --dump-outputs writes what the library returns for the same config."""
+    import bench
+    from mcaat_amd.configs import CONFIGS
+
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+           "--config", "tiny", "--dump-outputs", str(tmp_path / "out")]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["ms_per_step"] > 0
+    assert abs(d["value"] - d["config"]["kmers_total"] / (d["ms_per_step"] / 1e3)) / d["value"] < 1e-6
+    for key in ("e2e", "post_path", "fastq_ingest", "cpu_baseline"):
+        assert d[key] is None
+    assert "span" not in d
+
+    cfg = CONFIGS["tiny"]
+    reads = M.Reads.synth(gpu_ctx, cfg["spec"])
+    g = M.Graph.build(gpu_ctx, reads, cfg["k"])
+    want = bench.dump_arrays(g.size, g.cycle_finder(M.CfParams(threshold_multiplicity=cfg["thr"]), as_arrays=True))
+    g.free()
+    reads.free()
+    assert want["cycle_nodes"].size > 0 and want["sdbg_edges"][0] == d["config"]["sdbg_edges_D"]
+    assert sorted(os.listdir(tmp_path / "out")) == sorted(n + ".npy" for n in want)
+    for name, a in want.items():
+        got = np.load(tmp_path / "out" / (name + ".npy"))
+        assert got.dtype == np.float64 and np.array_equal(got, a), name
+
+
 def test_host_library_exports_every_declared_symbol():
     """libmcaat_host.so (include/mcaat_host.h): the downstream steps' C ABI."""
     from mcaat_amd import downstream as DS

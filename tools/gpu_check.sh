@@ -2,7 +2,7 @@
 #   bash tools/gpu_check.sh tests "<pytest -k expr>"   selected GPU tests
 #   bash tools/gpu_check.sh suite                       the whole GPU suite + smoke
 #   bash tools/gpu_check.sh abq [c3|c2|c5] [steps]      quick timing (tools/abq.sh)
-#   bash tools/gpu_check.sh bench                       the driver's default bench line
+#   bash tools/gpu_check.sh bench                       the full bench line (bench.py --full), kept in bench.log
 #   bash tools/gpu_check.sh rccl1 [c3]                  the sharded build's stages at one RCCL rank
 #                                                       (second build; the exchanges are local copies)
 #   bash tools/gpu_check.sh shard2 [c3]                 2 shm ranks vs one GPU, kernels profiled per rank
@@ -24,8 +24,8 @@ case "$what" in
   abq)
     CFG=${1:-c3} STEPS=${2:-3} bash tools/abq.sh default ;;
   bench)
-    timeout -k 10 900 python -u bench.py > gpurun_out/bench.log 2>&1 || { tail -30 gpurun_out/bench.log; exit 1; }
-    tail -1 gpurun_out/bench.log ;;
+    timeout -k 10 900 python -u bench.py --full > bench.log 2>&1 || { tail -30 bench.log; exit 1; }
+    tail -1 bench.log ;;
   rccl1)
     rm -f gpurun_out/rccl1.uid
     timeout -k 10 600 python -u tools/native_multi_check.py --world 1 --rank 0 --comm rccl --uid-file gpurun_out/rccl1.uid \
