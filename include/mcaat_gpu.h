@@ -432,6 +432,10 @@ int mcaat_set_knob(mcaat_ctx *ctx, const char *name, int64_t value);
  *   dist.walk_batch   walk tail rounds per batch between checks (default 8)
  *   dist.res_block_mb largest block set (MB) for fixed-block resolution; larger graphs keep the
  *                      routed rounds (default 64)
+ *   dist.grid_blocks  test knob: most blocks of every grid-stride launch of csrc/shard_cf.hip (the
+ *                      sharded adjacency, the per-shard CycleFinder, the unshard's splice; unset or 0:
+ *                      no effect), so that small inputs take every grid-stride loop with more items
+ *                      than threads
  *   dist.segs_at_one  1: one rank runs the descriptor exchange through the segment all-to-all too
  *                      (its self-copy path; default 0 keeps the buckets in place) */
 

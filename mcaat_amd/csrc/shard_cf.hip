@@ -1,5 +1,5 @@
-// shard_cf.hip — the per-shard CycleFinder of a multi-GPU run (round 5; BASELINE north_star:
-// "cycle_finder then runs per-shard with a boundary-edge exchange").
+// shard_cf.hip — the per-shard CycleFinder of a multi-GPU run: cycle_finder runs on every rank's
+// shard of the graph, with an exchange for what crosses a range boundary.
 //
 // The sharded build leaves every rank its BOSS-key range of the edges ([id_lo, id_lo + D_local)
 // of the global ids; mcaat_graph::sharded) instead of all-gathering the whole graph. Everything
@@ -23,6 +23,22 @@
 //       libstdc++ frame order), split over the ranks as before.
 // No rank holds, scans or peels the whole graph; results equal the one-GPU path bit for bit
 // (tests/test_native_multi.py).
+//
+// Layout of the file: the kernels, then the host side.
+//   Launch (run / run_at over launch_at): every kernel launch of the file. run() is for 1-D
+//       grid-stride kernels and holds the one grid policy, min(ceil(items / kBlk), cap), skipping
+//       empty launches; the test knob dist.grid_blocks lowers the cap to a few blocks so small
+//       inputs take every grid-stride loop more than once. run_at() is for kernels whose geometry
+//       carries meaning (one block per run, the Router's block ranges, single blocks, 2-D grids).
+//   Router: the routed exchange (send / reply; round_trip = request, answer, reply).
+//   ShardCf: the state and the stages of cycle_finder_sharded, in the order they run:
+//       tips_filter (windows_by_ranges | windows_by_messages, dist.win_ranges),
+//       peel (peel_prep, peel_walk [walk_tail_fixed, dist.walk_block], peel_jumps, peel_bref,
+//             peel_resolution [resolve_fixed | resolve_routed, dist.res_fixed], peel_removal),
+//       recount, dls_region, dls_search, fc_reach, find_cycle (fc_region, then the search);
+//       helpers: bit_prefix / list_bits, to_compact / to_global, select, region_bfs (bfs_dev | bfs,
+//       dist.bfs_sync), gather_region.
+//   sdbg_finish_sharded (adjacency_by_ranges | by messages, dist.adj_ranges), graph_unshard.
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
@@ -93,6 +109,48 @@ Owners owners_of(const mcaat_graph *g, const Comm &comm) {
 }
 
 __device__ __forceinline__ bool bit_of(const uint64_t *bm, uint64_t i) { return (bm[i >> 6] >> (i & 63)) & 1; }
+
+// first position in the ascending a[lo, hi) whose value is not below q
+__device__ __forceinline__ uint64_t lb_range(const uint64_t *a, uint64_t lo, uint64_t hi, uint64_t q) {
+    while (lo < hi) {
+        const uint64_t mid = (lo + hi) >> 1;
+        if (a[mid] < q) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// ---------------------------------------------------------------- launches
+// every launch of the file: the arguments converted to the kernel's parameter types (a DevBuf's
+// pointer to a pointer to const), the launch checked
+template <class... P, class... A>
+void launch_at(hipStream_t st, dim3 grid, dim3 block, void (*k)(P...), A &&...a) {
+    hipLaunchKernelGGL(k, grid, block, 0, st, static_cast<P>(a)...);
+    LAUNCH_OK();
+}
+
+struct Launch {
+    hipStream_t st;
+    unsigned cap;  // most blocks of a grid-stride launch (0: grid_for's own limit)
+    // per_cu: 16 blocks a compute unit (the D-wide kernels); dist.grid_blocks (a test knob) lowers
+    // either cap to that many blocks
+    Launch(const mcaat_ctx *ctx, bool per_cu = true) : st(ctx->stream), cap(per_cu ? (unsigned)ctx->n_cu * 16 : 0) {
+        const int64_t t = knob(ctx, "dist.grid_blocks", 0);
+        if (t > 0 && (cap == 0 || (uint64_t)t < cap)) cap = (unsigned)std::min<int64_t>(t, 65535);
+    }
+    // the grid of a 1-D grid-stride kernel over m items (the one place that decides it)
+    unsigned grid(uint64_t m) const { return cap ? grid_for(m, kBlk, cap) : grid_for(m, kBlk); }
+    // a grid-stride kernel over m items, kBlk threads a block; no items: no launch
+    template <class... P, class... A>
+    void run(uint64_t m, void (*k)(P...), A &&...a) const {
+        if (m) launch_at(st, dim3(grid(m)), dim3(kBlk), k, std::forward<A>(a)...);
+    }
+    // a kernel whose geometry carries meaning (dist.grid_blocks reaches it only through grid())
+    template <class... P, class... A>
+    void run_at(dim3 blocks, dim3 threads, void (*k)(P...), A &&...a) const {
+        launch_at(st, blocks, threads, k, std::forward<A>(a)...);
+    }
+};
 
 // ---------------------------------------------------------------- Router
 // Request / message slots of W 64-bit words, each with a destination rank (kNoDest: an empty
@@ -277,16 +335,11 @@ struct Router {
         rt.base.alloc((uint64_t)std::max(rt.G, 1) * N);
         const int NW = N + (extra_sum ? 1 : 0);
         DevBuf<uint64_t> tot(NW);
-        if (extra_sum) {
-            hipLaunchKernelGGL(k_set_word, dim3(1), dim3(1), 0, st, tot.p + N, extra);
-            LAUNCH_OK();
-        }
+        if (extra_sum) launch_at(st, dim3(1), dim3(1), k_set_word, tot.p + N, extra);
         double t0 = now();
         if (n) {
-            hipLaunchKernelGGL(k_route_count, dim3(rt.G), dim3(kBlk), 0, st, dest, n, rt.per, N, cnt.p);
-            LAUNCH_OK();
-            hipLaunchKernelGGL(k_route_offsets, dim3(1), dim3(1024), 0, st, (const uint32_t *)cnt.p, rt.G, N, rt.base.p, tot.p);
-            LAUNCH_OK();
+            launch_at(st, dim3(rt.G), dim3(kBlk), k_route_count, dest, n, rt.per, N, cnt.p);
+            launch_at(st, dim3(1), dim3(1024), k_route_offsets, cnt.p, rt.G, N, rt.base.p, tot.p);
         } else {
             HIP_OK(hipMemsetAsync(tot.p, 0, 8 * N, st));
         }
@@ -325,11 +378,9 @@ struct Router {
         rt.in.alloc((rt.n_in ? rt.n_in : 1) * W);
         // the send buffer has a hole where this rank's own records would be (they go to rt.in)
         DevBuf<uint64_t> sendb((N > 1 && rt.sent ? rt.sent : 1) * W);
-        if (rt.sent) {
-            hipLaunchKernelGGL(k_route_place<false>, dim3(rt.G), dim3(kBlk), 0, st, rec, W, dest, n, rt.per, N,
-                               (const uint64_t *)rt.base.p, sendb.p, R, rt.in.p + rt.in_off[R] * W, rt.out_off[R]);
-            LAUNCH_OK();
-        }
+        if (rt.sent)
+            launch_at(st, dim3(rt.G), dim3(kBlk), k_route_place<false>, rec, W, dest, n, rt.per, N, rt.base.p, sendb.p, R,
+                      rt.in.p + rt.in_off[R] * W, rt.out_off[R]);
         if (!keep) rt.base.release();
         std::vector<uint64_t> sb(N), rb(N), so(N), ro(N);
         for (int q = 0; q < N; ++q) {
@@ -365,14 +416,23 @@ struct Router {
         }
         sb[R] = rb[R] = 0;  // read in place
         if (N > 1) comm.alltoallv_dev(ans, sb.data(), back.p, rb.data(), so.data(), ro.data());
-        if (rt.sent) {
-            hipLaunchKernelGGL(k_route_place<true>, dim3(rt.G), dim3(kBlk), 0, st, (const uint64_t *)back.p, Wa, rt.dest,
-                               rt.n, rt.per, N, (const uint64_t *)rt.base.p, out, R, ans + rt.in_off[R] * Wa,
-                               rt.out_off[R]);
-            LAUNCH_OK();
-        }
+        if (rt.sent)
+            launch_at(st, dim3(rt.G), dim3(kBlk), k_route_place<true>, back.p, Wa, rt.dest, rt.n, rt.per, N, rt.base.p, out, R,
+                      ans + rt.in_off[R] * Wa, rt.out_off[R]);
         // (no synchronise: `out` is read by kernels or d2h on the same stream)
         ++rounds;
+    }
+    // One request / answer / reply round over the filled slots q / dest (n of them, one word
+    // each): the requests go to their ranks, answer(in, m, ans) writes one word per received
+    // record (called where this rank received any; the exchanges run on every rank), and the
+    // answers land in out[slot] (slots without a request keep what out held).
+    template <class F>
+    void round_trip(const uint64_t *q, const uint8_t *dest, uint64_t n, uint64_t *out, F &&answer) {
+        Routed r;
+        send(q, 1, dest, n, r, true);
+        DevBuf<uint64_t> ans(r.n_in + 1);
+        if (r.n_in) answer(r.in.p, r.n_in, ans.p);
+        reply(r, ans.p, 1, out);
     }
 };
 
@@ -388,6 +448,30 @@ __device__ __forceinline__ uint64_t wave_reserve(bool f, unsigned long long *cur
     }
     const unsigned long long below = lane ? mask & (~0ull >> (64 - lane)) : 0ull;
     return base + (uint64_t)__popcll(below);
+}
+
+// Fixed blocks, one per rank (word 0 of a block: its record count; rank R's own block is
+// self_blk, rank d's send + d * stride): every lane with d >= 0 appends one record to the block
+// of rank d, grouped by wave — one ballot per distinct destination in the wave and one count
+// atomic by the group's first lane. Each lane's position goes to its store(blk, at, end) within
+// its group's turn (blk: the block, at: the record's position in it, end: the block's count
+// after the group, for a capacity check): the payload and the overflow handling are the caller's.
+template <class Store>
+__device__ __forceinline__ void blk_append(int d, int R, uint64_t *send, uint64_t stride, uint64_t *self_blk, Store store) {
+    unsigned long long pend = __ballot(d >= 0);
+    while (pend) {
+        const int lead = __ffsll((long long)pend) - 1;
+        const int dd = __shfl(d, lead);
+        const unsigned long long mk = __ballot(d == dd);
+        uint64_t *blk = dd == R ? self_blk : send + (uint64_t)dd * stride;
+        uint64_t base = 0;
+        if ((int)(threadIdx.x & 63) == lead) base = atomicAdd((unsigned long long *)blk, (unsigned long long)__popcll(mk));
+        base = __shfl(base, lead);
+        if (d == dd)
+            store(blk, base + __builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0)),
+                  base + __popcll(mk));
+        pend &= ~mk;
+    }
 }
 
 uint64_t read_u64(mcaat_ctx *ctx, const unsigned long long *d) {
@@ -414,13 +498,7 @@ __device__ __forceinline__ uint64_t lb_local(const uint64_t *key, uint64_t n, co
     if (q < base) return 0;
     const uint64_t p = (q - base) >> shift;
     if (p >= np) return n;
-    uint64_t lo = dir[p], hi = dir[p + 1];
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (key[mid] < q) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
+    return lb_range(key, dir[p], dir[p + 1], q);
 }
 
 // two queries per edge: [2i] the target node's first edge (key prefix of s[1..k-1]W), [2i+1]
@@ -497,14 +575,7 @@ __global__ void __launch_bounds__(kBlk) k_count_less(const uint64_t *key, uint64
                                                      uint64_t *out) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= nq) return;
-    const uint64_t q = qs[t];
-    uint64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (key[mid] < q) lo = mid + 1;
-        else hi = mid;
-    }
-    out[t] = lo;
+    out[t] = lb_range(key, 0, n, qs[t]);
 }
 
 struct TgtRanges {  // this rank's four target ranges O_W(r), fetched
@@ -513,16 +584,6 @@ struct TgtRanges {  // this rank's four target ranges O_W(r), fetched
     uint64_t len[4];
     uint64_t g0[4];          // global id of the first
 };
-
-__device__ __forceinline__ uint64_t lb_arr(const uint64_t *a, uint64_t n, uint64_t q) {
-    uint64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (a[mid] < q) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
 
 constexpr int kRunT = 1024, kRunB = 2048, kRunMax = kRunB + 16, kRunCap = 3072;
 // bounds[5 r] = local start of run r (group aligned), bounds[5 r + 1 + W] = its first owned
@@ -543,7 +604,7 @@ __global__ void __launch_bounds__(kBlk) k_run_bounds(const uint64_t *key, uint64
             uint64_t b;
             if (r == 0) b = 0;
             else if (s >= n) b = T.len[W];
-            else b = lb_arr(T.key[W], T.len[W], (((uint64_t)W * top) | (key[s] >> 4)) << 2);
+            else b = lb_range(T.key[W], 0, T.len[W], (((uint64_t)W * top) | (key[s] >> 4)) << 2);
             bounds[5 * r + 1 + W] = b;
         }
     }
@@ -587,11 +648,11 @@ __global__ void __launch_bounds__(kRunT) k_adj_ranges(const uint64_t *key, uint6
         unsigned m = 0;
         if (staged) {
             const uint64_t *rk = okey + off[W];
-            const uint32_t x = (uint32_t)lb_arr(rk, len[W], qk);
+            const uint32_t x = (uint32_t)lb_range(rk, 0, len[W], qk);
             lo = a[W] + x;
             for (uint32_t i = x; i < len[W] && (rk[i] >> 2) == Rt; ++i) m |= 1u << (rk[i] & 3);
         } else {
-            lo = lb_arr(T.key[W], T.len[W], qk);
+            lo = lb_range(T.key[W], 0, T.len[W], qk);
             for (uint64_t i = lo; i < T.len[W] && (T.key[W][i] >> 2) == Rt; ++i) m |= 1u << (T.key[W][i] & 3);
         }
         out_info[s0 + j] = (T.g0[W] + lo) | ((uint64_t)m << kIdxBits);
@@ -887,22 +948,19 @@ __global__ void __launch_bounds__(kBlk) k_bits_list(const uint64_t *bm, uint64_t
     }
 }
 
+// the position of x in the ascending a[0, n), kNo when it is not there
+__device__ __forceinline__ uint64_t find_sorted(const uint64_t *a, uint64_t n, uint64_t x) {
+    const uint64_t lo = lb_range(a, 0, n, x);
+    return lo < n && a[lo] == x ? lo : kNo;
+}
+
 // a search region's ids: the position of each edge id in the region's ascending gid list (its
 // compact id; ~0 when it is not in the region), and back (~0 for positions past the list);
-// grid-stride (ShardCf::grid caps the grid)
+// grid-stride (Launch::grid caps the grid)
 __global__ void __launch_bounds__(kBlk) k_gid_find(const uint64_t *gid, uint64_t rn, const uint64_t *ids, uint64_t m,
                                                    uint64_t *out) {
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += stride) {
-        const uint64_t x = ids[i];
-        uint64_t lo = 0, hi = rn;
-        while (lo < hi) {
-            const uint64_t mid = (lo + hi) >> 1;
-            if (gid[mid] < x) lo = mid + 1;
-            else hi = mid;
-        }
-        out[i] = (lo < rn && gid[lo] == x) ? lo : ~0ULL;
-    }
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += stride) out[i] = find_sorted(gid, rn, ids[i]);
 }
 __global__ void __launch_bounds__(kBlk) k_gid_of(const uint64_t *gid, uint64_t rn, const uint64_t *c, uint64_t m,
                                                  uint64_t *out) {
@@ -999,7 +1057,7 @@ __global__ void __launch_bounds__(kBlk) k_walk(const uint64_t *in, uint64_t m, c
     }
 }
 
-// (round 6) the walk's tail in fixed blocks (once every rank's records in flight fit one block):
+// the walk's tail in fixed blocks (dist.walk_block; once every rank's records in flight fit one block):
 // the records of every source block (blockIdx.y; this rank's own from self_in) walk, and what goes
 // out lands in the destination's block of `send` or in self_out (word 0 of a block: its records)
 __global__ void __launch_bounds__(kBlk) k_walk_fx(const uint64_t *recv, const uint64_t *self_in, int R, uint64_t P,
@@ -1018,26 +1076,14 @@ __global__ void __launch_bounds__(kBlk) k_walk_fx(const uint64_t *recv, const ui
             x = blk[2 + 2 * j];
             if (!walk_one(r, x, kind, nx, o, merge_known, to)) to = -1;
         }
-        unsigned long long pend = __ballot(to >= 0);
-        while (pend) {
-            const int lead = __ffsll((long long)pend) - 1;
-            const int dd = __shfl(to, lead);
-            const unsigned long long mk = __ballot(to == dd);
-            uint64_t *ob = dd == R ? self_out : send + (uint64_t)dd * (1 + 2 * P);
-            uint64_t base = 0;
-            if ((int)(threadIdx.x & 63) == lead) base = atomicAdd((unsigned long long *)ob, (unsigned long long)__popcll(mk));
-            base = __shfl(base, lead);
-            if (to == dd) {
-                // (records never multiply: a block holds every record in flight when the tail began)
-                const uint64_t at = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0));
-                ob[1 + 2 * at] = r;
-                ob[2 + 2 * at] = x;
-            }
-            pend &= ~mk;
-        }
+        // (records never multiply: a block holds every record in flight when the tail began)
+        blk_append(to, R, send, 1 + 2 * P, self_out, [&](uint64_t *ob, uint64_t at, uint64_t) {
+            ob[1 + 2 * at] = r;
+            ob[2 + 2 * at] = x;
+        });
     }
 }
-// zero the counts of N blocks of `stride` words, and of one more block
+// zero the counts of N blocks of `stride` words, and of one more block (null: none)
 __global__ void k_blk_zero(uint64_t *blocks, int N, uint64_t stride, uint64_t *one) {
     const int t = threadIdx.x;
     if (t < N) blocks[(uint64_t)t * stride] = 0;
@@ -1355,11 +1401,12 @@ __global__ void __launch_bounds__(kBlk) k_bfs_claim(const uint64_t *q, uint64_t 
     }
 }
 
-// (round 6) The region BFS with its hops back to back on the device. A hop's requests go into
+// The region BFS with its hops back to back on the device (the default; dist.bfs_sync=1 takes
+// k_bfs_req / k_bfs_claim above, one routed exchange per hop). A hop's requests go into
 // fixed-capacity blocks, one per rank (word 0: the block's request count, then up to its capacity
 // of requests; this rank's own block is separate and holds a whole frontier), exchanged by
 // Comm::alltoall_fixed, which the RCCL transport leaves queued on the stream: no host round trip
-// per hop (round 5's form took three: the count all-gather, the all-to-all, the next frontier's
+// per hop (the routed form takes three: the count all-gather, the all-to-all, the next frontier's
 // size). Frontier sizes stay in device memory (one counter per hop). A block or frontier that
 // overflows its capacity sets a flag (with the count it needed); the host reads the flags once
 // after the last hop, and if any rank overflowed every rank runs the BFS again with larger blocks.
@@ -1369,11 +1416,6 @@ struct BfsCaps {
 };
 // flags: [0] a peer block overflowed, [1] the most requests one peer block needed,
 // [2] the own block or a frontier overflowed, [3] the largest own block / frontier needed
-__global__ void __launch_bounds__(kBlk) k_bfs_zero(uint64_t *send, int N, uint64_t P, uint64_t *self_blk) {
-    const int t = threadIdx.x;
-    if (t < N) send[(uint64_t)t * (1 + P)] = 0;
-    if (t == 0) self_blk[0] = 0;
-}
 __global__ void __launch_bounds__(kBlk) k_bfs_req_dev(const uint64_t *front, const unsigned long long *nf_p,
                                                       const uint64_t *out_info, const uint64_t *in_info, int backward,
                                                       Owners o, uint64_t *send, BfsCaps c, uint64_t *self_blk,
@@ -1398,31 +1440,18 @@ __global__ void __launch_bounds__(kBlk) k_bfs_req_dev(const uint64_t *front, con
             rec = lo | (pos << kIdxBits);
             if (pos) d = owner_of_id(o, lo);
         }
-        // one count atomic per destination present in the wave
-        unsigned long long pend = __ballot(d >= 0);
-        while (pend) {
-            const int lead = __ffsll((long long)pend) - 1;
-            const int dd = __shfl(d, lead);
-            const unsigned long long m = __ballot(d == dd);
-            const bool self = dd == o.R;
-            uint64_t *blk = self ? self_blk : send + (uint64_t)dd * (1 + c.P);
+        blk_append(d, o.R, send, 1 + c.P, self_blk, [&](uint64_t *blk, uint64_t at, uint64_t end) {
+            const bool self = blk == self_blk;
             const uint64_t cap = self ? c.F : c.P;
-            uint64_t base = 0;
-            if ((int)(threadIdx.x & 63) == lead) base = atomicAdd((unsigned long long *)blk, (unsigned long long)__popcll(m));
-            base = __shfl(base, lead);
-            if (d == dd) {
-                const uint64_t at = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
-                if (at < cap) blk[1 + at] = rec;
-                if (at + 1 == base + __popcll(m) && base + __popcll(m) > cap) {  // the wave's last slot
-                    atomicOr(&flags[self ? 2 : 0], 1ull);
-                    atomicMax(&flags[self ? 3 : 1], (unsigned long long)(base + __popcll(m)));
-                }
+            if (at < cap) blk[1 + at] = rec;
+            if (at + 1 == end && end > cap) {  // the last slot of the wave's records for d
+                atomicOr(&flags[self ? 2 : 0], 1ull);
+                atomicMax(&flags[self ? 3 : 1], (unsigned long long)end);
             }
-            pend &= ~m;
-        }
+        });
     }
 }
-// (round 6) fixed-block request / reply (branch resolution): slot j's request q[j] goes to rank
+// fixed-block request / reply (branch resolution, dist.res_fixed): slot j's request q[j] goes to rank
 // dest[j] (kNoDest: none) into that rank's block (word 0: count; this rank's own requests into
 // its own block, which holds every slot), its position kept in pos[j]; the answers come back in
 // the same positions
@@ -1432,22 +1461,10 @@ __global__ void __launch_bounds__(kBlk) k_fx_post(const uint64_t *q, const uint8
     for (uint64_t j0 = (uint64_t)blockIdx.x * blockDim.x; j0 < m; j0 += stride) {
         const uint64_t j = j0 + threadIdx.x;
         const int d = j < m && dest[j] != kNoDest ? (int)dest[j] : -1;
-        unsigned long long pend = __ballot(d >= 0);
-        while (pend) {
-            const int lead = __ffsll((long long)pend) - 1;
-            const int dd = __shfl(d, lead);
-            const unsigned long long mk = __ballot(d == dd);
-            uint64_t *blk = dd == R ? self_blk : send + (uint64_t)dd * (1 + P);
-            uint64_t base = 0;
-            if ((int)(threadIdx.x & 63) == lead) base = atomicAdd((unsigned long long *)blk, (unsigned long long)__popcll(mk));
-            base = __shfl(base, lead);
-            if (d == dd) {
-                const uint64_t at = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0));
-                blk[1 + at] = q[j];  // (P holds every slot of the largest rank: no overflow)
-                pos[j] = (uint32_t)at;
-            }
-            pend &= ~mk;
-        }
+        blk_append(d, R, send, 1 + P, self_blk, [&](uint64_t *blk, uint64_t at, uint64_t) {
+            blk[1 + at] = q[j];  // (P holds every slot of the largest rank: no overflow)
+            pos[j] = (uint32_t)at;
+        });
     }
 }
 // the owner: each received request's state (as k_st_ans) into the reply block at its position
@@ -1507,25 +1524,11 @@ __global__ void __launch_bounds__(kBlk) k_bfs_claim_dev(const uint64_t *recv, co
     }
 }
 
-// a BFS hop on a region replica (compact ids, every rank alike): the valid successors not seen yet
-__global__ void __launch_bounds__(kBlk) k_cbfs(GraphView g, const uint64_t *front, uint64_t nf, uint64_t *seen, uint64_t *next,
-                                               unsigned long long *nn) {
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < nf; j += stride) {
-        uint64_t out[4];
-        const int od = dev_outgoing(g, front[j], out);
-        for (int b = 0; b < od; ++b) {
-            const uint64_t x = out[b], bit = 1ULL << (x & 63);
-            if (!(atomicOr((unsigned long long *)&seen[x >> 6], bit) & bit)) next[atomicAdd(nn, 1ull)] = x;
-        }
-    }
-}
-
-// (round 6) the same hop with the frontier size read on the device: the hops run back to back
-// with no host round trip between them (the frontier buffers hold every edge of the replica, and
-// each edge joins a frontier at most once)
-__global__ void __launch_bounds__(kBlk) k_cbfs_dev(GraphView g, const uint64_t *front, const unsigned long long *nf_p,
-                                                   uint64_t *seen, uint64_t *next, unsigned long long *nn) {
+// a BFS hop on a region replica (compact ids, every rank alike): the valid successors not seen
+// yet. The frontier size is read on the device (the previous hop's counter), so hops can run back
+// to back with no host round trip between them
+__global__ void __launch_bounds__(kBlk) k_cbfs(GraphView g, const uint64_t *front, const unsigned long long *nf_p,
+                                               uint64_t *seen, uint64_t *next, unsigned long long *nn) {
     const uint64_t nf = *nf_p, stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < nf; j += stride) {
         uint64_t out[4];
@@ -1555,16 +1558,6 @@ __global__ void __launch_bounds__(kBlk) k_region_list(const uint64_t *reg, uint6
 __global__ void __launch_bounds__(kBlk) k_word_popc64(const uint64_t *bm, uint64_t nw, uint64_t *cnt) {
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; w < nw; w += stride) cnt[w] = __popcll(bm[w]);
-}
-
-__device__ __forceinline__ uint64_t find_sorted(const uint64_t *a, uint64_t n, uint64_t x) {
-    uint64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (a[mid] < x) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo < n && a[lo] == x ? lo : kNo;
 }
 
 // the compact replica: ids, multiplicities, adjacency words with compact first ids (a window
@@ -1606,276 +1599,27 @@ __global__ void __launch_bounds__(kBlk) k_region_words(const uint64_t *rec, uint
 }
 
 // ---------------------------------------------------------------- host drivers
-struct ShardCf {
-    mcaat_graph *g;
-    mcaat_ctx *ctx;
-    Comm &comm;
-    Router rt;
-    Owners o;
-    hipStream_t st;
-    uint64_t n, nwl;
-    unsigned grid(uint64_t m, unsigned cap_per_cu = 16) const { return grid_for(m, kBlk, (unsigned)ctx->n_cu * cap_per_cu); }
-    ShardCf(mcaat_graph *gr, Comm &c)
-        : g(gr), ctx(gr->ctx), comm(c), rt(gr->ctx, c), o(owners_of(gr, c)), st(gr->ctx->stream), n(gr->D_local),
-          nwl((gr->D_local + 63) / 64) {}
-
-    // the set bits of a local bitmap (nwl words) as local indices, ascending
-    // (nw: the bitmap's words, default this rank's)
-    uint64_t list_bits(const uint64_t *bm, DevBuf<uint64_t> &out, uint64_t nw = ~0ULL) {
-        if (nw == ~0ULL) nw = nwl;
-        DevBuf<uint64_t> pc(nw + 1), wpre(nw + 1);
-        HIP_OK(hipMemsetAsync(pc.p + nw, 0, 8, st));
-        uint64_t cnt = 0;
-        if (nw) {
-            hipLaunchKernelGGL(k_word_popc64, dim3(grid(nw)), dim3(kBlk), 0, st, bm, nw, pc.p);
-            LAUNCH_OK();
-            size_t tmp = 0;
-            HIP_OK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, pc.p, wpre.p, (size_t)(nw + 1), st));
-            DevBuf<uint8_t> t(tmp);
-            HIP_OK(hipcub::DeviceScan::ExclusiveSum(t.p, tmp, pc.p, wpre.p, (size_t)(nw + 1), st));
-            d2h(ctx, &cnt, wpre.p + nw, 8);
-        }
-        out.alloc(cnt ? cnt : 1);
-        if (cnt) {
-            hipLaunchKernelGGL(k_bits_list, dim3(grid(nw * 64)), dim3(kBlk), 0, st, bm, nw, (const uint64_t *)wpre.p, out.p);
-            LAUNCH_OK();
-        }
-        return cnt;
-    }
-
-    // (round 6) a search region's id translations on the device, where its gid list stays (its
-    // 8 B per edge were read back whole before: C3 at one rank, 20 ms for the DLS region's 5.5 M
-    // ids and 16 ms of host binary searches for the candidates)
-    // edge ids -> compact ids of region rg (rn edges); every id must lie in the region
-    std::vector<uint64_t> to_compact(const mcaat_graph &rg, uint64_t rn, const std::vector<uint64_t> &ids) {
-        const uint64_t m = ids.size();
-        std::vector<uint64_t> c(m);
-        if (!m) return c;
-        DevBuf<uint64_t> d(m), o(m);
-        h2d(ctx, d.p, ids.data(), 8 * m);
-        hipLaunchKernelGGL(k_gid_find, dim3(grid(m)), dim3(kBlk), 0, st, (const uint64_t *)rg.gid.p, rn,
-                           (const uint64_t *)d.p, m, o.p);
-        LAUNCH_OK();
-        d2h(ctx, c.data(), o.p, 8 * m);
-        for (uint64_t x : c)
-            if (x == ~0ULL) throw Error(MCAAT_E_INVALID, "per-shard CycleFinder: a start is outside its region");
-        return c;
-    }
-    // compact ids (device list of m) -> edge ids (~0 past the region's edges)
-    std::vector<uint64_t> to_global(const mcaat_graph &rg, uint64_t rn, const uint64_t *c, uint64_t m) {
-        std::vector<uint64_t> g(m);
-        if (!m) return g;
-        DevBuf<uint64_t> o(m);
-        hipLaunchKernelGGL(k_gid_of, dim3(grid(m)), dim3(kBlk), 0, st, (const uint64_t *)rg.gid.p, rn, c, m, o.p);
-        LAUNCH_OK();
-        d2h(ctx, g.data(), o.p, 8 * m);
-        return g;
-    }
-    std::vector<uint64_t> to_global(const mcaat_graph &rg, uint64_t rn, const std::vector<uint64_t> &c) {
-        if (c.empty()) return {};
-        DevBuf<uint64_t> d(c.size());
-        h2d(ctx, d.p, c.data(), 8 * c.size());
-        return to_global(rg, rn, d.p, c.size());
-    }
-
-    // in[j] where flags[j] != 0, in order (hipcub select); returns the count
-    uint64_t select(const uint64_t *in, const uint8_t *flags, uint64_t m, uint64_t *out) {
-        DevBuf<unsigned long long> num(1);
-        size_t tmp = 0;
-        HIP_OK(hipcub::DeviceSelect::Flagged(nullptr, tmp, in, flags, out, num.p, (size_t)m, st));
-        DevBuf<uint8_t> t(tmp ? tmp : 1);
-        HIP_OK(hipcub::DeviceSelect::Flagged(t.p, tmp, in, flags, out, num.p, (size_t)m, st));
-        return read_u64(ctx, num.p);
-    }
-
-    uint64_t sum(uint64_t v) {
-        uint64_t t = 0;
-        for (uint64_t x : comm.allgather_one(v)) t += x;
-        return t;
-    }
-
-    // BFS of `rounds` hops from the frontier (local indices, already seen and marked)
-    void bfs(DevBuf<uint64_t> &front, uint64_t nf, uint64_t rounds, bool backward, const uint64_t *gs, uint64_t *reg,
-             uint64_t *seen) {
-        DevBuf<unsigned long long> c(2);
-        for (uint64_t h = 0; h < rounds; ++h) {
-            DevBuf<uint64_t> q(nf ? nf : 1);
-            DevBuf<uint8_t> dest(nf ? nf : 1);
-            HIP_OK(hipMemsetAsync(c.p, 0, 16, st));
-            if (nf) {
-                hipLaunchKernelGGL(k_bfs_req, dim3(grid(nf)), dim3(kBlk), 0, st, (const uint64_t *)front.p, nf,
-                                   (const uint64_t *)g->out_info.p, (const uint64_t *)g->in_info.p, (int)backward, o, q.p,
-                                   dest.p);
-                LAUNCH_OK();
-            }
-            Routed r;
-            rt.send(q.p, 1, dest.p, nf, r, false);
-            if (!r.total) break;  // every rank's frontier was empty (the routing's count exchange says so)
-            // each received window adds at most 16 edges
-            DevBuf<uint64_t> next(16 * r.n_in + 1);
-            if (r.n_in) {
-                hipLaunchKernelGGL(k_bfs_claim, dim3(grid(r.n_in)), dim3(kBlk), 0, st, (const uint64_t *)r.in.p, r.n_in,
-                                   g->id_lo, n, gs, (const uint64_t *)g->valid.p, reg, seen, next.p, c.p + 1);
-                LAUNCH_OK();
-            }
-            nf = r.n_in ? read_u64(ctx, c.p + 1) : 0;
-            front = std::move(next);
-        }
-    }
-
-    // (round 6) the BFS from this rank's edges `ids` (global ids), hops back to back on the device
-    // (see k_bfs_req_dev); reg and seen are cleared and seeded here, and cleared again for a run
-    // with larger blocks after an overflow on any rank
-    void bfs_dev(const std::vector<uint64_t> &ids, uint64_t rounds, bool backward, const uint64_t *gs, uint64_t *reg,
-                 uint64_t *seen) {
-        const int N = comm.world, R = comm.rank;
-        const uint64_t m = ids.size();
-        DevBuf<uint64_t> dids(m + 1);
-        if (m) h2d(ctx, dids.p, ids.data(), 8 * m);
-        BfsCaps c;
-        // (C3 at 8 ranks needs up to 2^15 requests a block: 2^16 is 512 KB a peer and hop)
-        c.P = (uint64_t)std::max<int64_t>(64, knob(ctx, "dist.bfs_block", 1 << 16));
-        if (!knob_set(ctx, "dist.bfs_block")) c.P = std::max(c.P, ctx->bfs_block[backward]);
-        // a frontier or the own block: the whole local graph in the end (each edge joins one
-        // frontier at most once), a sixteenth of it (and the seeds) first
-        c.F = std::min<uint64_t>(n + 1, std::max<uint64_t>({m + 1, n / 16 + 1, 1u << 20}));
-        if (knob_set(ctx, "dist.bfs_frontier")) c.F = std::max<uint64_t>(m + 1, (uint64_t)knob(ctx, "dist.bfs_frontier", 1));
-        for (int attempt = 0;; ++attempt) {
-            HIP_OK(hipMemsetAsync(reg, 0, 8 * (nwl + 1), st));
-            HIP_OK(hipMemsetAsync(seen, 0, 8 * (nwl + 1), st));
-            DevBuf<uint64_t> fr[2];
-            fr[0].alloc(c.F);
-            fr[1].alloc(c.F);
-            DevBuf<uint64_t> send((uint64_t)N * (1 + c.P)), recv((uint64_t)N * (1 + c.P)), self_blk(1 + c.F);
-            DevBuf<unsigned long long> cnt(rounds + 1), flags(4);
-            HIP_OK(hipMemsetAsync(cnt.p, 0, cnt.bytes(), st));
-            HIP_OK(hipMemsetAsync(flags.p, 0, flags.bytes(), st));
-            if (m) {
-                hipLaunchKernelGGL(k_bfs_seed, dim3(grid(m)), dim3(kBlk), 0, st, (const uint64_t *)dids.p, m, g->id_lo, n, gs,
-                                   reg, seen, fr[0].p);
-                LAUNCH_OK();
-                h2d(ctx, cnt.p, &m, 8);
-            }
-            const unsigned gq = grid(std::min<uint64_t>(c.F, 1u << 22));
-            const unsigned gc = grid(std::min<uint64_t>(std::max(c.F, c.P), 1u << 22)) / (unsigned)N + 1;
-            for (uint64_t h = 0; h < rounds; ++h) {
-                hipLaunchKernelGGL(k_bfs_zero, dim3(1), dim3(kBlk), 0, st, send.p, N, c.P, self_blk.p);
-                LAUNCH_OK();
-                hipLaunchKernelGGL(k_bfs_req_dev, dim3(gq), dim3(kBlk), 0, st, (const uint64_t *)fr[h & 1].p,
-                                   (const unsigned long long *)(cnt.p + h), (const uint64_t *)g->out_info.p,
-                                   (const uint64_t *)g->in_info.p, (int)backward, o, send.p, c, self_blk.p, flags.p);
-                LAUNCH_OK();
-                comm.alltoall_fixed(send.p, 8 * (1 + c.P), recv.p);
-                hipLaunchKernelGGL(k_bfs_claim_dev, dim3(gc, (unsigned)N), dim3(kBlk), 0, st, (const uint64_t *)recv.p,
-                                   (const uint64_t *)self_blk.p, R, c, g->id_lo, n, gs, (const uint64_t *)g->valid.p, reg,
-                                   seen, fr[(h + 1) & 1].p, cnt.p + h + 1, flags.p);
-                LAUNCH_OK();
-            }
-            unsigned long long fl[4];
-            d2h(ctx, fl, flags.p, 32);
-            // every rank takes the same decision (the exchanges are collective)
-            const auto all = comm.allgather_vec(std::vector<uint64_t>{fl[0] | fl[2], fl[1], fl[3]});
-            bool again = false;
-            uint64_t needP = 0, needF = 0;
-            for (int r = 0; r < N; ++r) {
-                again |= all[3 * r] != 0;
-                needP = std::max<uint64_t>(needP, all[3 * r + 1]);
-                needF = std::max<uint64_t>(needF, all[3 * r + 2]);
-            }
-            if (!again) {
-                ctx->bfs_block[backward] = c.P;
-                break;
-            }
-            if (attempt >= 8) throw Error(MCAAT_E_CAPACITY, "per-shard region BFS: blocks still overflow");
-            // a hop after an overflowed one saw a partial frontier: twice what was counted, at least
-            c.P = std::max(c.P, next_pow2(2 * needP));
-            c.F = std::min<uint64_t>(n + 1, std::max(c.F, 2 * needF));
-            if (needF > c.F) c.F = n + 1;
-            if (verbose())
-                fprintf(stderr, "[mcaat] shard %d: region BFS again with %llu-request blocks, %llu-edge frontiers\n", R,
-                        (unsigned long long)c.P, (unsigned long long)c.F);
-        }
-    }
-
-    // every rank: the compact replica of the groups marked in reg on all ranks
-    // returns the region's edge count (rg->gid: their ascending ids, kept on the device)
-    uint64_t gather_region(const uint64_t *reg, mcaat_graph *rg) {
-        DevBuf<uint64_t> pc(nwl + 1), wpre(nwl + 1);
-        HIP_OK(hipMemsetAsync(pc.p + nwl, 0, 8, st));
-        uint64_t mine = 0;
-        if (nwl) {
-            hipLaunchKernelGGL(k_word_popc64, dim3(grid(nwl)), dim3(kBlk), 0, st, reg, nwl, pc.p);
-            LAUNCH_OK();
-            size_t tmp = 0;
-            HIP_OK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, pc.p, wpre.p, (size_t)(nwl + 1), st));
-            DevBuf<uint8_t> t(tmp);
-            HIP_OK(hipcub::DeviceScan::ExclusiveSum(t.p, tmp, pc.p, wpre.p, (size_t)(nwl + 1), st));
-            d2h(ctx, &mine, wpre.p + nwl, 8);
-        }
-        DevBuf<uint64_t> rec(4 * (mine ? mine : 1));
-        if (mine) {
-            hipLaunchKernelGGL(k_region_list, dim3(grid(nwl * 64)), dim3(kBlk), 0, st, reg, n, (const uint64_t *)wpre.p,
-                               g->id_lo, (const uint64_t *)g->out_info.p, (const uint64_t *)g->in_info.p,
-                               (const uint16_t *)g->mult.p, (const uint64_t *)g->valid.p, rec.p);
-            LAUNCH_OK();
-        }
-        verbose_mark(ctx, "region.list");
-        const std::vector<uint64_t> per = comm.allgather_one(mine);
-        uint64_t rn = 0;
-        std::vector<uint64_t> bytes(comm.world);
-        for (int r = 0; r < comm.world; ++r) rn += per[r], bytes[r] = 32 * per[r];
-        DevBuf<uint64_t> all(4 * (rn ? rn : 1));
-        HIP_OK(hipStreamSynchronize(st));
-        if (rn) comm.allgatherv_dev(rec.p, all.p, bytes.data());
-        verbose_mark(ctx, "region.gather");
-        // rank order = ascending ids (every rank's list ascends): compact id = position
-        const uint64_t D = rn + 16;  // + the null group
-        rg->ctx = ctx;
-        rg->k = g->k;
-        rg->D = D;
-        rg->gid.alloc(D);
-        rg->mult.alloc(mcaat_graph::mult_entries(D));
-        rg->out_info.alloc(D);
-        rg->in_info.alloc(D);
-        rg->valid.alloc(mcaat_graph::bitmap_words(D));
-        HIP_OK(hipMemsetAsync(rg->mult.p, 0, rg->mult.bytes(), st));
-        HIP_OK(hipMemsetAsync(rg->out_info.p, 0, rg->out_info.bytes(), st));
-        HIP_OK(hipMemsetAsync(rg->in_info.p, 0, rg->in_info.bytes(), st));
-        HIP_OK(hipMemsetAsync(rg->valid.p, 0, rg->valid.bytes(), st));
-        HIP_OK(hipMemsetAsync(rg->gid.p, 0xFF, rg->gid.bytes(), st));
-        if (rn) {
-            hipLaunchKernelGGL(k_region_build, dim3(grid(rn)), dim3(kBlk), 0, st, (const uint64_t *)all.p, rn, rg->gid.p,
-                               rg->mult.p, rg->out_info.p, rg->in_info.p);
-            LAUNCH_OK();
-            hipLaunchKernelGGL(k_region_words, dim3(grid(rn)), dim3(kBlk), 0, st, (const uint64_t *)all.p, rn,
-                               (const uint64_t *)rg->gid.p, rg->mult.p, rg->out_info.p, rg->in_info.p, rg->valid.p);
-            LAUNCH_OK();
-        }
-        rg->all_valid = false;
-        verbose_mark(ctx, "region.build");
-        return rn;
-    }
-};
-
-}  // namespace
+// edges per exchange of a chunked request / response pass (dist.adj_chunk) and the number of
+// exchanges: the most any rank needs, as every rank takes part in all of them
+uint64_t exchange_chunks(mcaat_ctx *ctx, Comm &comm, uint64_t n, uint64_t &chunk) {
+    chunk = (uint64_t)std::max<int64_t>(1024, knob(ctx, "dist.adj_chunk", 1LL << 26));
+    uint64_t n_chunks = (n + chunk - 1) / chunk;
+    for (uint64_t x : comm.allgather_one(n_chunks)) n_chunks = std::max(n_chunks, x);
+    return n_chunks;
+}
 
 // ---------------------------------------------------------------- sharded adjacency
-namespace {
 void finish_valid(mcaat_ctx *ctx, mcaat_graph *g) {
     const uint64_t n = g->D_local;
     g->valid.alloc(mcaat_graph::bitmap_words(n));
     HIP_OK(hipMemsetAsync(g->valid.p, 0, g->valid.bytes(), ctx->stream));
-    if (n) {
-        hipLaunchKernelGGL(k_ones, dim3(grid_for((n + 63) / 64, kBlk)), dim3(kBlk), 0, ctx->stream, g->valid.p, n);
-        LAUNCH_OK();
-    }
+    Launch(ctx, false).run((n + 63) / 64, k_ones, g->valid.p, n);
     g->all_valid = true;
     HIP_OK(hipStreamSynchronize(ctx->stream));
 }
 
 // O_W(r) for every rank: O[W * (N + 1) + r] (kept in g->tgt_lo)
 std::vector<uint64_t> target_ranges(mcaat_ctx *ctx, Comm &comm, const mcaat_graph *g) {
-    hipStream_t st = ctx->stream;
     const int k = g->k, N = comm.world;
     const uint64_t n = g->D_local, D = g->D;
     // every rank's first key (empty ranks: the next rank's, or none)
@@ -1900,9 +1644,9 @@ std::vector<uint64_t> target_ranges(mcaat_ctx *ctx, Comm &comm, const mcaat_grap
     if (n) {
         DevBuf<uint64_t> dq(qs.size()), dc(qs.size());
         h2d(ctx, dq.p, qs.data(), 8 * qs.size());
-        hipLaunchKernelGGL(k_count_less, dim3(grid_for(qs.size(), kBlk)), dim3(kBlk), 0, st, (const uint64_t *)g->key.p, n,
-                           (const uint64_t *)dq.p, (int)qs.size(), dc.p);
-        LAUNCH_OK();
+        // one thread per query
+        launch_at(ctx->stream, dim3((unsigned)((qs.size() + kBlk - 1) / kBlk)), dim3(kBlk), k_count_less, g->key.p, n, dq.p,
+                  (int)qs.size(), dc.p);
         d2h(ctx, cl.data(), dc.p, 8 * cl.size());
     }
     const std::vector<uint64_t> all = comm.allgather_vec(cl);
@@ -1955,7 +1699,8 @@ struct RangeX {
     }
 };
 
-// out_info / in_info of the rank's edges through its four target ranges (k_adj_ranges above)
+// out_info / in_info of the rank's edges through its four target ranges (k_adj_ranges above;
+// the default, dist.adj_ranges=1)
 void adjacency_by_ranges(mcaat_ctx *ctx, Comm &comm, mcaat_graph *g) {
     hipStream_t st = ctx->stream;
     const int k = g->k, R = comm.rank;
@@ -1979,13 +1724,10 @@ void adjacency_by_ranges(mcaat_ctx *ctx, Comm &comm, mcaat_graph *g) {
     // runs of the own edges, then out_info and the ranges' in_info
     const uint64_t nruns = (n + kRunB - 1) / kRunB;
     if (nruns) {
+        const Launch L(ctx, false);
         DevBuf<uint64_t> bounds(5 * (nruns + 1));
-        hipLaunchKernelGGL(k_run_bounds, dim3(grid_for(nruns + 1, kBlk)), dim3(kBlk), 0, st, (const uint64_t *)g->key.p, n, k,
-                           T, nruns, bounds.p);
-        LAUNCH_OK();
-        hipLaunchKernelGGL(k_adj_ranges, dim3((unsigned)nruns), dim3(kRunT), 0, st, (const uint64_t *)g->key.p, id_lo, k, T,
-                           (const uint64_t *)bounds.p, g->out_info.p);
-        LAUNCH_OK();
+        L.run(nruns + 1, k_run_bounds, g->key.p, n, k, T, nruns, bounds.p);
+        L.run_at(dim3((unsigned)nruns), dim3(kRunT), k_adj_ranges, g->key.p, id_lo, k, T, bounds.p, g->out_info.p);  // a block per run
     } else {
         for (int W = 0; W < 4; ++W)  // no sources: the ranges (empty or not) have no predecessors here
             if (T.len[W]) HIP_OK(hipMemsetAsync(ti[W].p, 0, 8 * T.len[W], st));
@@ -1999,11 +1741,36 @@ void adjacency_by_ranges(mcaat_ctx *ctx, Comm &comm, mcaat_graph *g) {
                 R, (unsigned long long)n, (unsigned long long)T.len[0], (unsigned long long)T.len[1],
                 (unsigned long long)T.len[2], (unsigned long long)T.len[3]);
 }
+
+// the same by messages (dist.adj_ranges=0): two queries per edge to the owners of its target node
+// and its predecessor group, answered from the owners' radix directories, in chunks of edges
+void adjacency_by_messages(mcaat_ctx *ctx, Comm &comm, mcaat_graph *g) {
+    const uint64_t n = g->D_local;
+    const Launch L(ctx);
+    Router rt(ctx, comm);
+    const Owners o = owners_of(g, comm);
+    uint64_t chunk;
+    const uint64_t n_chunks = exchange_chunks(ctx, comm, n, chunk);
+    KernelTimer kt(ctx, "adjacency", 32.0 * (double)n);
+    for (uint64_t c = 0; c < n_chunks; ++c) {
+        const uint64_t i0 = std::min(n, c * chunk), m = std::min(n, i0 + chunk) - i0;
+        DevBuf<uint64_t> q(2 * m + 1);
+        DevBuf<uint8_t> dest(2 * m + 1);
+        L.run(m, k_adj_queries, g->key.p, i0, m, g->k, o, q.p, dest.p);
+        // the answers land in their request slots (every slot has an owner)
+        rt.round_trip(q.p, dest.p, 2 * m, q.p, [&](const uint64_t *in, uint64_t m_in, uint64_t *ans) {
+            L.run(m_in, k_adj_answer, g->key.p, n, g->id_lo, g->dir.p, g->dir_base, g->dir_shift, g->dir_n, in, m_in, ans);
+        });
+        L.run(m, k_adj_store, q.p, i0, m, g->out_info.p, g->in_info.p);
+    }
+    kt.stop();
+    if (verbose())
+        fprintf(stderr, "[mcaat] shard %d: adjacency of %llu edges, %llu exchanges, %llu queries\n", comm.rank,
+                (unsigned long long)n, (unsigned long long)rt.rounds, (unsigned long long)rt.records);
+}
 }  // namespace
 
 void sdbg_finish_sharded(mcaat_ctx *ctx, Comm &comm, mcaat_graph *g) {
-    hipStream_t st = ctx->stream;
-    const int k = g->k;
     const uint64_t n = g->D_local;
     // local radix directory over the range's keys (dist.dir_edges edges per prefix, default 2)
     uint64_t kmin = 0, kmax = 0;
@@ -2019,109 +1786,296 @@ void sdbg_finish_sharded(mcaat_ctx *ctx, Comm &comm, mcaat_graph *g) {
     g->dir_shift = shift;
     g->dir_base = kmin;
     g->dir_n = np;
-    hipLaunchKernelGGL(k_sdir, dim3(grid_for(n + 1, kBlk, (unsigned)ctx->n_cu * 16)), dim3(kBlk), 0, st, g->key.p, n, kmin,
-                       shift, np, g->dir.p);
-    LAUNCH_OK();
+    Launch(ctx).run(n + 1, k_sdir, g->key.p, n, kmin, shift, np, g->dir.p);
     g->out_info.alloc(n ? n : 1);
     g->in_info.alloc(n ? n : 1);
-    if (knob(ctx, "dist.adj_ranges", 1)) {
-        adjacency_by_ranges(ctx, comm, g);
-        finish_valid(ctx, g);
-        return;
-    }
-    Router rt(ctx, comm);
-    const Owners o = owners_of(g, comm);
-    // chunks of edges: two queries each; every rank takes part in as many exchanges
-    const uint64_t chunk = (uint64_t)std::max<int64_t>(1024, knob(ctx, "dist.adj_chunk", 1LL << 26));
-    uint64_t n_chunks = (n + chunk - 1) / chunk;
-    for (uint64_t x : comm.allgather_one(n_chunks)) n_chunks = std::max(n_chunks, x);
-    KernelTimer kt(ctx, "adjacency", 32.0 * (double)n);
-    for (uint64_t c = 0; c < n_chunks; ++c) {
-        const uint64_t i0 = std::min(n, c * chunk), m = std::min(n, i0 + chunk) - i0;
-        DevBuf<uint64_t> q(2 * m + 1);
-        DevBuf<uint8_t> dest(2 * m + 1);
-        if (m) {
-            hipLaunchKernelGGL(k_adj_queries, dim3(grid_for(m, kBlk, (unsigned)ctx->n_cu * 16)), dim3(kBlk), 0, st, g->key.p,
-                               i0, m, k, o, q.p, dest.p);
-            LAUNCH_OK();
-        }
-        Routed r;
-        rt.send(q.p, 1, dest.p, 2 * m, r, true);
-        DevBuf<uint64_t> ans(r.n_in + 1), a2(2 * m + 1);
-        if (r.n_in) {
-            hipLaunchKernelGGL(k_adj_answer, dim3(grid_for(r.n_in, kBlk, (unsigned)ctx->n_cu * 16)), dim3(kBlk), 0, st,
-                               (const uint64_t *)g->key.p, n, g->id_lo, (const uint64_t *)g->dir.p, kmin, shift, np,
-                               (const uint64_t *)r.in.p, r.n_in, ans.p);
-            LAUNCH_OK();
-        }
-        rt.reply(r, ans.p, 1, a2.p);
-        if (m) {
-            hipLaunchKernelGGL(k_adj_store, dim3(grid_for(m, kBlk, (unsigned)ctx->n_cu * 16)), dim3(kBlk), 0, st,
-                               (const uint64_t *)a2.p, i0, m, g->out_info.p, g->in_info.p);
-            LAUNCH_OK();
-        }
-    }
-    kt.stop();
+    if (knob(ctx, "dist.adj_ranges", 1)) adjacency_by_ranges(ctx, comm, g);
+    else adjacency_by_messages(ctx, comm, g);
     finish_valid(ctx, g);
-    if (verbose())
-        fprintf(stderr, "[mcaat] shard %d: adjacency of %llu edges, %llu exchanges, %llu queries\n", comm.rank,
-                (unsigned long long)n, (unsigned long long)rt.rounds, (unsigned long long)rt.records);
 }
 
 // ---------------------------------------------------------------- per-shard CycleFinder
-void cycle_finder_sharded(mcaat_graph *g, const mcaat_cf_params &p, mcaat_cycles *out, Comm &comm) {
-    mcaat_ctx *ctx = g->ctx;
-    hipStream_t st = ctx->stream;
-    StageTimer timer(ctx);
-    if (!g->all_valid)
-        throw Error(MCAAT_E_INVALID, "per-shard CycleFinder needs the graph as built (every edge valid); unshard it first");
-    g->all_valid = false;
-    ShardCf s(g, comm);
-    const uint64_t n = s.n, nwl = s.nwl, id_lo = g->id_lo;
-    // collectives per stage (kstats "xr_<stage>".launches): the bulk-synchronous rounds that bound
-    // this path at N ranks (DESIGN.md §7's model)
-    uint64_t xr_last = comm.n_coll, xq_last = comm.n_queued;
-    auto xr = [&](const char *stage) {
-        ctx->kstats[std::string("xr_") + stage].launches += comm.n_coll - xr_last;
-        ctx->kstats[std::string("xq_") + stage].launches += comm.n_queued - xq_last;  // of them queued
-        xr_last = comm.n_coll;
-        xq_last = comm.n_queued;
-    };
-    DevBuf<unsigned long long> cnt(8);
-    HIP_OK(hipMemsetAsync(cnt.p, 0, 64, st));
+namespace {
+struct ShardCf {
+    mcaat_graph *g;
+    mcaat_ctx *ctx;
+    Comm &comm;
+    const Launch L;  // this context's stream, the D-wide cap
+    hipStream_t st;
+    const mcaat_cf_params &p;
+    mcaat_cycles *out;
+    Router rt;
+    Owners o;
+    const uint64_t n, nwl, id_lo;
+    const uint64_t radius;  // hops of a search region: cycle_max_length + 1
+    const bool bfs_sync;    // dist.bfs_sync=1: region BFS and FindCycle reach hop by hop, the host waiting on each
 
-    // 1-2. CollectTips (fresh graph) and InvalidateMultiplicityOneNodes: local
-    DevBuf<uint64_t> post(nwl + 1), seed(nwl + 1);
-    HIP_OK(hipMemsetAsync(post.p + nwl, 0, 8, st));
-    HIP_OK(hipMemsetAsync(seed.p + nwl, 0, 8, st));
-    if (n) {
-        hipLaunchKernelGGL(k_sh_filter, dim3(s.grid(nwl * 64)), dim3(kBlk), 0, st, (const uint16_t *)g->mult.p,
-                           (const uint64_t *)g->out_info.p, n, post.p, seed.p, cnt.p);
-        LAUNCH_OK();
+    // ---- what crosses a stage boundary: the stage that writes it -> the last one that reads it
+    DevBuf<unsigned long long> cnt;   // counters: [0..2] tips_filter, [7] peel_resolution, [0] recount
+    DevBuf<uint64_t> post;            // filter-valid bits: tips_filter -> peel_removal (freed with cbits)
+    DevBuf<uint64_t> seed;            // tips of the fresh graph: tips_filter -> peel_prep
+    DevBuf<uint8_t> kind;             // filtered out-window and predecessor flags: tips_filter -> peel_removal
+    DevBuf<uint8_t> stt;              // state of the non-unary edges: peel_prep -> peel_removal (allocated with kind)
+    DevBuf<uint64_t> nx;              // successor / claim / jump words: tips_filter -> peel_removal
+    DevBuf<uint64_t> cbits;           // ChunkStartNodes' filter, a bit per local edge: tips_filter -> recount
+    bool merge_known = false;         // kMerge marks where unary chains meet (dist.win_ranges): tips_filter -> peel_walk
+    std::vector<uint64_t> cand_mine;  // this rank's candidates still valid, ascending ids: recount -> dls_region
+    DevBuf<uint64_t> gs, reg, seen;   // group starts, region and BFS marks: dls_region -> fc_region
+    mcaat_graph rg;                   // the DepthLevelSearch region's replica: dls_region -> fc_reach
+    uint64_t rn = 0;                  //   its edges
+    std::vector<uint64_t> cand_all;   // every rank's candidates, ascending: dls_region -> dls_search
+    std::vector<uint64_t> starts;     // FindCycle's starts, bucket order: dls_search -> find_cycle
+    std::vector<uint64_t> fwd;        // FindCycle's forward reach, ascending ids: fc_reach -> fc_region
+    struct Peel {                     // the peel's own, freed when it ends
+        DevBuf<uint64_t> rl, bl;      // rulers and branches (local indices): peel_prep -> peel_removal
+        uint64_t nr = 0, nb = 0;
+        DevBuf<uint64_t> ref;         // per branch slot its successor's reference (kPad: unused): peel_bref -> peel_resolution
+        uint64_t walk_rounds = 0, jump_rounds = 0, res_rounds = 0, n_rm_rulers = 0;  // the MCAAT_VERBOSE line
+    };
+
+    ShardCf(mcaat_graph *gr, Comm &c, const mcaat_cf_params &pa, mcaat_cycles *res)
+        : g(gr), ctx(gr->ctx), comm(c), L(gr->ctx), st(gr->ctx->stream), p(pa), out(res), rt(gr->ctx, c),
+          o(owners_of(gr, c)), n(gr->D_local), nwl((gr->D_local + 63) / 64), id_lo(gr->id_lo),
+          radius((uint64_t)pa.cycle_max_length + 1), bfs_sync(knob(gr->ctx, "dist.bfs_sync", 0) != 0) {}
+
+    // launches on this context's stream with its cap (see Launch)
+    unsigned grid(uint64_t m) const { return L.grid(m); }
+    template <class... P, class... A>
+    void run(uint64_t m, void (*k)(P...), A &&...a) const {
+        L.run(m, k, std::forward<A>(a)...);
     }
-    // filtered out-windows and the candidates' in-windows from their owners
-    DevBuf<uint8_t> kind(n + 4), stt(n + 4);
-    DevBuf<uint64_t> nx(n ? n : 1);
-    HIP_OK(hipMemsetAsync(kind.p, 0, kind.bytes(), st));
-    DevBuf<uint64_t> cbits(nwl + 1);  // ChunkStartNodes' filter, one bit per local edge
-    HIP_OK(hipMemsetAsync(cbits.p, 0, cbits.bytes(), st));
-    // chunks of local edges per exchange (every rank runs as many): bounded transient memory
-    const uint64_t chunk = (uint64_t)std::max<int64_t>(1024, knob(ctx, "dist.adj_chunk", 1LL << 26));
-    uint64_t n_chunks = (n + chunk - 1) / chunk;
-    for (uint64_t x : comm.allgather_one(n_chunks)) n_chunks = std::max(n_chunks, x);
-    const bool win_ranges = knob(ctx, "dist.win_ranges", 1) != 0;  // (also: merge points known, kMerge)
-    if (win_ranges) {
-        n_chunks = 0;  // (the message form below is skipped)
+    template <class... P, class... A>
+    void run_at(dim3 blocks, dim3 threads, void (*k)(P...), A &&...a) const {
+        L.run_at(blocks, threads, k, std::forward<A>(a)...);
+    }
+
+    // ---------------- helpers
+    // a bitmap's words: their popcounts (pc), wpre[w] = the set bits before word w (nw + 1 entries
+    // each), and the total; both buffers live as long as the caller keeps the result
+    struct BitPrefix {
+        DevBuf<uint64_t> pc, wpre;
+        uint64_t total = 0;
+    };
+    BitPrefix bit_prefix(const uint64_t *bm, uint64_t nw) {
+        BitPrefix b;
+        b.pc.alloc(nw + 1);
+        b.wpre.alloc(nw + 1);
+        HIP_OK(hipMemsetAsync(b.pc.p + nw, 0, 8, st));
+        if (nw) {
+            run(nw, k_word_popc64, bm, nw, b.pc.p);
+            size_t tmp = 0;
+            HIP_OK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, b.pc.p, b.wpre.p, (size_t)(nw + 1), st));
+            DevBuf<uint8_t> t(tmp);
+            HIP_OK(hipcub::DeviceScan::ExclusiveSum(t.p, tmp, b.pc.p, b.wpre.p, (size_t)(nw + 1), st));
+            d2h(ctx, &b.total, b.wpre.p + nw, 8);
+        }
+        return b;
+    }
+    // the set bits of a bitmap of nw words as indices, ascending
+    uint64_t list_bits(const uint64_t *bm, DevBuf<uint64_t> &out_list, uint64_t nw) {
+        const BitPrefix b = bit_prefix(bm, nw);
+        out_list.alloc(b.total ? b.total : 1);
+        if (b.total) run(nw * 64, k_bits_list, bm, nw, b.wpre.p, out_list.p);
+        return b.total;
+    }
+
+    // a search region's id translations on the device, where its gid list stays
+    // edge ids -> compact ids of region r (rn_ edges); every id must lie in the region
+    std::vector<uint64_t> to_compact(const mcaat_graph &r, uint64_t rn_, const std::vector<uint64_t> &ids) {
+        const uint64_t m = ids.size();
+        std::vector<uint64_t> c(m);
+        if (!m) return c;
+        DevBuf<uint64_t> d(m), dc(m);
+        h2d(ctx, d.p, ids.data(), 8 * m);
+        run(m, k_gid_find, r.gid.p, rn_, d.p, m, dc.p);
+        d2h(ctx, c.data(), dc.p, 8 * m);
+        for (uint64_t x : c)
+            if (x == ~0ULL) throw Error(MCAAT_E_INVALID, "per-shard CycleFinder: a start is outside its region");
+        return c;
+    }
+    // compact ids (device list of m) -> edge ids (~0 past the region's edges)
+    std::vector<uint64_t> to_global(const mcaat_graph &r, uint64_t rn_, const uint64_t *c, uint64_t m) {
+        std::vector<uint64_t> ids(m);
+        if (!m) return ids;
+        DevBuf<uint64_t> d(m);
+        run(m, k_gid_of, r.gid.p, rn_, c, m, d.p);
+        d2h(ctx, ids.data(), d.p, 8 * m);
+        return ids;
+    }
+    std::vector<uint64_t> to_global(const mcaat_graph &r, uint64_t rn_, const std::vector<uint64_t> &c) {
+        if (c.empty()) return {};
+        DevBuf<uint64_t> d(c.size());
+        h2d(ctx, d.p, c.data(), 8 * c.size());
+        return to_global(r, rn_, d.p, c.size());
+    }
+
+    // in[j] where flags[j] != 0, in order (hipcub select); returns the count
+    uint64_t select(const uint64_t *in, const uint8_t *flags, uint64_t m, uint64_t *sel) {
+        DevBuf<unsigned long long> num(1);
+        size_t tmp = 0;
+        HIP_OK(hipcub::DeviceSelect::Flagged(nullptr, tmp, in, flags, sel, num.p, (size_t)m, st));
+        DevBuf<uint8_t> t(tmp ? tmp : 1);
+        HIP_OK(hipcub::DeviceSelect::Flagged(t.p, tmp, in, flags, sel, num.p, (size_t)m, st));
+        return read_u64(ctx, num.p);
+    }
+
+    uint64_t sum(uint64_t v) {
+        uint64_t t = 0;
+        for (uint64_t x : comm.allgather_one(v)) t += x;
+        return t;
+    }
+
+    // ---------------- region BFS
+    // `rounds` hops from the frontier (local indices, already seen and marked), one routed
+    // exchange and two host waits per hop
+    void bfs(DevBuf<uint64_t> &front, uint64_t nf, uint64_t rounds, bool backward) {
+        DevBuf<unsigned long long> c(2);
+        for (uint64_t h = 0; h < rounds; ++h) {
+            DevBuf<uint64_t> q(nf ? nf : 1);
+            DevBuf<uint8_t> dest(nf ? nf : 1);
+            HIP_OK(hipMemsetAsync(c.p, 0, 16, st));
+            run(nf, k_bfs_req, front.p, nf, g->out_info.p, g->in_info.p, (int)backward, o, q.p, dest.p);
+            Routed r;
+            rt.send(q.p, 1, dest.p, nf, r, false);
+            if (!r.total) break;  // every rank's frontier was empty (the routing's count exchange says so)
+            // each received window adds at most 16 edges
+            DevBuf<uint64_t> next(16 * r.n_in + 1);
+            run(r.n_in, k_bfs_claim, r.in.p, r.n_in, id_lo, n, gs.p, g->valid.p, reg.p, seen.p, next.p, c.p + 1);
+            nf = r.n_in ? read_u64(ctx, c.p + 1) : 0;
+            front = std::move(next);
+        }
+    }
+
+    // the same from this rank's edges `ids` (global ids) with the hops back to back on the device
+    // (see k_bfs_req_dev); reg and seen are cleared and seeded here, and cleared again for a run
+    // with larger blocks after an overflow on any rank
+    void bfs_dev(const std::vector<uint64_t> &ids, uint64_t rounds, bool backward) {
+        const int N = comm.world, R = comm.rank;
+        const uint64_t m = ids.size();
+        DevBuf<uint64_t> dids(m + 1);
+        if (m) h2d(ctx, dids.p, ids.data(), 8 * m);
+        BfsCaps c;
+        // (C3 at 8 ranks needs up to 2^15 requests a block: 2^16 is 512 KB a peer and hop)
+        c.P = (uint64_t)std::max<int64_t>(64, knob(ctx, "dist.bfs_block", 1 << 16));
+        if (!knob_set(ctx, "dist.bfs_block")) c.P = std::max(c.P, ctx->bfs_block[backward]);
+        // a frontier or the own block: the whole local graph in the end (each edge joins one
+        // frontier at most once), a sixteenth of it (and the seeds) first
+        c.F = std::min<uint64_t>(n + 1, std::max<uint64_t>({m + 1, n / 16 + 1, 1u << 20}));
+        if (knob_set(ctx, "dist.bfs_frontier")) c.F = std::max<uint64_t>(m + 1, (uint64_t)knob(ctx, "dist.bfs_frontier", 1));
+        for (int attempt = 0;; ++attempt) {
+            HIP_OK(hipMemsetAsync(reg.p, 0, 8 * (nwl + 1), st));
+            HIP_OK(hipMemsetAsync(seen.p, 0, 8 * (nwl + 1), st));
+            DevBuf<uint64_t> fr[2];
+            fr[0].alloc(c.F);
+            fr[1].alloc(c.F);
+            DevBuf<uint64_t> send((uint64_t)N * (1 + c.P)), recv((uint64_t)N * (1 + c.P)), self_blk(1 + c.F);
+            DevBuf<unsigned long long> hops(rounds + 1), flags(4);  // hops[h]: the frontier size of hop h
+            HIP_OK(hipMemsetAsync(hops.p, 0, hops.bytes(), st));
+            HIP_OK(hipMemsetAsync(flags.p, 0, flags.bytes(), st));
+            if (m) {
+                run(m, k_bfs_seed, dids.p, m, id_lo, n, gs.p, reg.p, seen.p, fr[0].p);
+                h2d(ctx, hops.p, &m, 8);
+            }
+            // the frontier sizes are known on the device only: grids for the capacities
+            const dim3 gq(grid(std::min<uint64_t>(c.F, 1u << 22)));
+            const dim3 gc(grid(std::min<uint64_t>(std::max(c.F, c.P), 1u << 22)) / (unsigned)N + 1, (unsigned)N);
+            for (uint64_t h = 0; h < rounds; ++h) {
+                run_at(dim3(1), dim3(kBlk), k_blk_zero, send.p, N, 1 + c.P, self_blk.p);
+                run_at(gq, dim3(kBlk), k_bfs_req_dev, fr[h & 1].p, hops.p + h, g->out_info.p, g->in_info.p, (int)backward, o,
+                       send.p, c, self_blk.p, flags.p);
+                comm.alltoall_fixed(send.p, 8 * (1 + c.P), recv.p);
+                run_at(gc, dim3(kBlk), k_bfs_claim_dev, recv.p, self_blk.p, R, c, id_lo, n, gs.p, g->valid.p, reg.p, seen.p,
+                       fr[(h + 1) & 1].p, hops.p + h + 1, flags.p);
+            }
+            unsigned long long fl[4];
+            d2h(ctx, fl, flags.p, 32);
+            // every rank takes the same decision (the exchanges are collective)
+            const auto all = comm.allgather_vec(std::vector<uint64_t>{fl[0] | fl[2], fl[1], fl[3]});
+            bool again = false;
+            uint64_t needP = 0, needF = 0;
+            for (int r = 0; r < N; ++r) {
+                again |= all[3 * r] != 0;
+                needP = std::max<uint64_t>(needP, all[3 * r + 1]);
+                needF = std::max<uint64_t>(needF, all[3 * r + 2]);
+            }
+            if (!again) {
+                ctx->bfs_block[backward] = c.P;
+                break;
+            }
+            if (attempt >= 8) throw Error(MCAAT_E_CAPACITY, "per-shard region BFS: blocks still overflow");
+            // a hop after an overflowed one saw a partial frontier: twice what was counted, at least
+            c.P = std::max(c.P, next_pow2(2 * needP));
+            c.F = std::min<uint64_t>(n + 1, std::max(c.F, 2 * needF));
+            if (needF > c.F) c.F = n + 1;
+            if (verbose())
+                fprintf(stderr, "[mcaat] shard %d: region BFS again with %llu-request blocks, %llu-edge frontiers\n", R,
+                        (unsigned long long)c.P, (unsigned long long)c.F);
+        }
+    }
+
+    // the region (reg) within `rounds` hops, forward or backward, of this rank's edges `ids`
+    // (global ids): back to back on the device, or hop by hop (dist.bfs_sync=1)
+    void region_bfs(const std::vector<uint64_t> &ids, uint64_t rounds, bool backward) {
+        if (!bfs_sync) return bfs_dev(ids, rounds, backward);
+        HIP_OK(hipMemsetAsync(reg.p, 0, reg.bytes(), st));
+        HIP_OK(hipMemsetAsync(seen.p, 0, seen.bytes(), st));
+        const uint64_t m = ids.size();
+        DevBuf<uint64_t> dids(m + 1), front(m + 1);
+        if (m) h2d(ctx, dids.p, ids.data(), 8 * m);
+        run(m, k_bfs_seed, dids.p, m, id_lo, n, gs.p, reg.p, seen.p, front.p);
+        bfs(front, m, rounds, backward);
+    }
+
+    // every rank: the compact replica of the groups marked in reg on all ranks
+    // returns the region's edge count (r->gid: their ascending ids, kept on the device)
+    uint64_t gather_region(mcaat_graph *r) {
+        const BitPrefix b = bit_prefix(reg.p, nwl);
+        const uint64_t mine = b.total;
+        DevBuf<uint64_t> rec(4 * (mine ? mine : 1));
+        if (mine) run(nwl * 64, k_region_list, reg.p, n, b.wpre.p, id_lo, g->out_info.p, g->in_info.p, g->mult.p, g->valid.p, rec.p);
+        verbose_mark(ctx, "region.list");
+        const std::vector<uint64_t> per = comm.allgather_one(mine);
+        uint64_t total = 0;
+        std::vector<uint64_t> bytes(comm.world);
+        for (int q = 0; q < comm.world; ++q) total += per[q], bytes[q] = 32 * per[q];
+        DevBuf<uint64_t> all(4 * (total ? total : 1));
+        HIP_OK(hipStreamSynchronize(st));
+        if (total) comm.allgatherv_dev(rec.p, all.p, bytes.data());
+        verbose_mark(ctx, "region.gather");
+        // rank order = ascending ids (every rank's list ascends): compact id = position
+        const uint64_t D = total + 16;  // + the null group
+        r->ctx = ctx;
+        r->k = g->k;
+        r->D = D;
+        r->gid.alloc(D);
+        r->mult.alloc(mcaat_graph::mult_entries(D));
+        r->out_info.alloc(D);
+        r->in_info.alloc(D);
+        r->valid.alloc(mcaat_graph::bitmap_words(D));
+        HIP_OK(hipMemsetAsync(r->mult.p, 0, r->mult.bytes(), st));
+        HIP_OK(hipMemsetAsync(r->out_info.p, 0, r->out_info.bytes(), st));
+        HIP_OK(hipMemsetAsync(r->in_info.p, 0, r->in_info.bytes(), st));
+        HIP_OK(hipMemsetAsync(r->valid.p, 0, r->valid.bytes(), st));
+        HIP_OK(hipMemsetAsync(r->gid.p, 0xFF, r->gid.bytes(), st));
+        run(total, k_region_build, all.p, total, r->gid.p, r->mult.p, r->out_info.p, r->in_info.p);
+        run(total, k_region_words, all.p, total, r->gid.p, r->mult.p, r->out_info.p, r->in_info.p, r->valid.p);
+        r->all_valid = false;
+        verbose_mark(ctx, "region.build");
+        return total;
+    }
+
+    // ---------------- stage: tips + filter
+    // The filtered out-window of every edge (kind, the unary successor in nx), the predecessor
+    // flags and ChunkStartNodes' in-degree test (cbits) by target ranges (the default): the owners'
+    // filter bits of the four ranges pulled, a byte per range edge pushed back
+    void windows_by_ranges() {
         if (g->tgt_lo.empty()) g->tgt_lo = target_ranges(ctx, comm, g);
         const RangeX X{comm, comm.world, comm.rank, g->rank_lo, g->tgt_lo};
         TgtBytes T{};
         DevBuf<uint8_t> tpb[4], tf[4];
         {
             DevBuf<uint8_t> pb(n + 1);
-            if (n) {
-                hipLaunchKernelGGL(k_post_bytes, dim3(s.grid(n)), dim3(kBlk), 0, st, (const uint64_t *)post.p, n, pb.p);
-                LAUNCH_OK();
-            }
+            run(n, k_post_bytes, post.p, n, pb.p);
             for (int W = 0; W < 4; ++W) {
                 const uint64_t len = X.len(W);
                 tpb[W].alloc(len + 8);
@@ -2134,612 +2088,453 @@ void cycle_finder_sharded(mcaat_graph *g, const mcaat_cf_params &p, mcaat_cycles
                 T.len[W] = len;
             }
         }
-        if (n) {
-            hipLaunchKernelGGL(k_out_win, dim3(s.grid(n)), dim3(kBlk), 0, st, (const uint64_t *)post.p,
-                               (const uint64_t *)g->key.p, (const uint64_t *)g->out_info.p, n, T, kind.p, nx.p);
-            LAUNCH_OK();
-            hipLaunchKernelGGL(k_push_bytes, dim3(s.grid(n)), dim3(kBlk), 0, st, (const uint64_t *)post.p,
-                               (const uint64_t *)seed.p, (const uint64_t *)g->key.p, (const uint64_t *)g->out_info.p,
-                               (const uint8_t *)kind.p, n, id_lo, T, cnt.p);
-            LAUNCH_OK();
-        }
+        run(n, k_out_win, post.p, g->key.p, g->out_info.p, n, T, kind.p, nx.p);
+        run(n, k_push_bytes, post.p, seed.p, g->key.p, g->out_info.p, kind.p, n, id_lo, T, cnt.p);
         for (int W = 0; W < 4; ++W) tpb[W].release();
         DevBuf<uint8_t> inb(n + 1);
         HIP_OK(hipMemsetAsync(inb.p, 0, inb.bytes(), st));
         for (int W = 0; W < 4; ++W) X.push(tf[W].p, 1, W, inb.p);
-        if (n) {
-            hipLaunchKernelGGL(k_recv_bytes, dim3(s.grid(nwl * 64)), dim3(kBlk), 0, st, (const uint8_t *)inb.p,
-                               (const uint64_t *)post.p, (const uint16_t *)g->mult.p, (uint64_t)p.threshold_multiplicity,
-                               n, kind.p, nx.p, cbits.p);
-            LAUNCH_OK();
+        run(nwl * 64, k_recv_bytes, inb.p, post.p, g->mult.p, (uint64_t)p.threshold_multiplicity, n, kind.p, nx.p, cbits.p);
+    }
+    // the same by messages (dist.win_ranges=0): window requests to the owners, then the
+    // predecessor flags to the successors' owners, in chunks of local edges
+    void windows_by_messages(uint64_t chunk, uint64_t n_chunks) {
+        if (n_chunks) HIP_OK(hipMemsetAsync(nx.p, 0xFF, nx.bytes(), st));  // kNo: no successor word
+        for (uint64_t c = 0; c < n_chunks; ++c) {
+            const uint64_t a0 = std::min(n, c * chunk), a1 = std::min(n, a0 + chunk), m = a1 - a0;
+            DevBuf<uint64_t> q(2 * m + 1);
+            DevBuf<uint8_t> dest(2 * m + 1);
+            run(m, k_win_req, post.p, g->mult.p, g->out_info.p, g->in_info.p, a0, a1, (uint64_t)p.threshold_multiplicity, o, q.p,
+                dest.p);
+            // the answers land in their request slots
+            rt.round_trip(q.p, dest.p, 2 * m, q.p, [&](const uint64_t *in, uint64_t m_in, uint64_t *ans) {
+                run(m_in, k_win_ans, post.p, n, id_lo, in, m_in, ans);
+            });
+            run(m, k_win_apply, dest.p, q.p, a0, a1, g->out_info.p, g->in_info.p, id_lo, kind.p, nx.p, cbits.p);
+        }
+        // (after every window is in)
+        for (uint64_t c = 0; c < n_chunks; ++c) {
+            const uint64_t a0 = std::min(n, c * chunk), a1 = std::min(n, a0 + chunk), m = a1 - a0;
+            DevBuf<uint64_t> q(4 * m + 1);
+            DevBuf<uint8_t> dest(4 * m + 1);
+            run(m, k_flag_msgs, post.p, seed.p, kind.p, g->out_info.p, a0, a1, o, q.p, dest.p, cnt.p);
+            Routed r;
+            rt.send(q.p, 1, dest.p, 4 * m, r, false);
+            run(r.n_in, k_flag_apply, r.in.p, r.n_in, id_lo, kind.p);
         }
     }
-    if (n_chunks) HIP_OK(hipMemsetAsync(nx.p, 0xFF, nx.bytes(), st));  // kNo: no successor word
-    for (uint64_t c = 0; c < n_chunks; ++c) {
-        const uint64_t a0 = std::min(n, c * chunk), a1 = std::min(n, a0 + chunk), m = a1 - a0;
-        DevBuf<uint64_t> q(2 * m + 1);
-        DevBuf<uint8_t> dest(2 * m + 1);
-        if (m) {
-            hipLaunchKernelGGL(k_win_req, dim3(s.grid(m)), dim3(kBlk), 0, st, (const uint64_t *)post.p,
-                               (const uint16_t *)g->mult.p, (const uint64_t *)g->out_info.p, (const uint64_t *)g->in_info.p,
-                               a0, a1, (uint64_t)p.threshold_multiplicity, s.o, q.p, dest.p);
-            LAUNCH_OK();
-        }
-        Routed r;
-        s.rt.send(q.p, 1, dest.p, 2 * m, r, true);
-        DevBuf<uint64_t> ans(r.n_in + 1);
-        if (r.n_in) {
-            hipLaunchKernelGGL(k_win_ans, dim3(s.grid(r.n_in)), dim3(kBlk), 0, st, (const uint64_t *)post.p, n, id_lo,
-                               (const uint64_t *)r.in.p, r.n_in, ans.p);
-            LAUNCH_OK();
-        }
-        s.rt.reply(r, ans.p, 1, q.p);  // the answers land in their request slots
-        if (m) {
-            hipLaunchKernelGGL(k_win_apply, dim3(s.grid(m)), dim3(kBlk), 0, st, (const uint8_t *)dest.p,
-                               (const uint64_t *)q.p, a0, a1, (const uint64_t *)g->out_info.p, (const uint64_t *)g->in_info.p,
-                               id_lo, kind.p, nx.p, cbits.p);
-            LAUNCH_OK();
-        }
-    }
-    // predecessor flags, as messages to the successors' owners (after every window is in)
-    for (uint64_t c = 0; c < n_chunks; ++c) {
-        const uint64_t a0 = std::min(n, c * chunk), a1 = std::min(n, a0 + chunk), m = a1 - a0;
-        DevBuf<uint64_t> q(4 * m + 1);
-        DevBuf<uint8_t> dest(4 * m + 1);
-        if (m) {
-            hipLaunchKernelGGL(k_flag_msgs, dim3(s.grid(m)), dim3(kBlk), 0, st, (const uint64_t *)post.p,
-                               (const uint64_t *)seed.p, (const uint8_t *)kind.p, (const uint64_t *)g->out_info.p, a0, a1,
-                               s.o, q.p, dest.p, cnt.p);
-            LAUNCH_OK();
-        }
-        Routed r;
-        s.rt.send(q.p, 1, dest.p, 4 * m, r, false);
-        if (r.n_in) {
-            hipLaunchKernelGGL(k_flag_apply, dim3(s.grid(r.n_in)), dim3(kBlk), 0, st, (const uint64_t *)r.in.p, r.n_in,
-                               id_lo, kind.p);
-            LAUNCH_OK();
-        }
-    }
-    unsigned long long hc[4];
-    d2h(ctx, hc, cnt.p, 32);
-    {
+    // CollectTips (fresh graph) and InvalidateMultiplicityOneNodes: local; then the windows
+    void tips_filter() {
+        cnt.alloc(8);
+        HIP_OK(hipMemsetAsync(cnt.p, 0, 64, st));
+        post.alloc(nwl + 1);
+        seed.alloc(nwl + 1);
+        HIP_OK(hipMemsetAsync(post.p + nwl, 0, 8, st));
+        HIP_OK(hipMemsetAsync(seed.p + nwl, 0, 8, st));
+        run(nwl * 64, k_sh_filter, g->mult.p, g->out_info.p, n, post.p, seed.p, cnt.p);
+        kind.alloc(n + 4);
+        stt.alloc(n + 4);
+        nx.alloc(n ? n : 1);
+        cbits.alloc(nwl + 1);
+        HIP_OK(hipMemsetAsync(kind.p, 0, kind.bytes(), st));
+        HIP_OK(hipMemsetAsync(cbits.p, 0, cbits.bytes(), st));
+        // (the chunk count is agreed in either form: the same collectives on every path)
+        uint64_t chunk;
+        const uint64_t n_chunks = exchange_chunks(ctx, comm, n, chunk);
+        merge_known = knob(ctx, "dist.win_ranges", 1) != 0;
+        if (merge_known) windows_by_ranges();
+        else windows_by_messages(chunk, n_chunks);
+        unsigned long long hc[4];
+        d2h(ctx, hc, cnt.p, 32);
         const auto all = comm.allgather_vec(std::vector<uint64_t>{hc[0], hc[1], hc[2]});
         out->stats[0] = out->stats[1] = out->stats[3] = 0;
         for (int r = 0; r < comm.world; ++r)
             out->stats[0] += all[3 * r], out->stats[1] += all[3 * r + 1], out->stats[3] += all[3 * r + 2];
     }
-    timer.mark("tips_filter");
-    xr("tips_filter");
 
-    // 3. RecursiveReduction: rulers, walks, pointer jumping, branch resolution, removal
-    // ruler density: a walk's rounds are the rank crossings of the longest walk (≈ (N-1)/N x its
-    // length), so more ranks take denser rulers (C3, two shm ranks: 1 in 4 / 8 / 16 / 64 unary
-    // edges -> 35 / 77 / 135 / 489 walk rounds, 1.13 / 0.60 / 0.36 / 0.20 G records)
-    const uint64_t rmask = (uint64_t)std::max<int64_t>(0, knob(ctx, "dist.ruler_mask", comm.world > 2 ? 3 : 15));
-    DevBuf<uint64_t> rl, bl;
-    uint64_t nr = 0, nb = 0;
-    {
+    // ---------------- stage: peel (RecursiveReduction)
+    // rulers, the states of the non-unary edges, the lists of rulers and branches
+    void peel_prep(Peel &pl) {
+        // ruler density: a walk's rounds are the rank crossings of the longest walk (≈ (N-1)/N x its
+        // length), so more ranks take denser rulers (C3, two shm ranks: 1 in 4 / 8 / 16 / 64 unary
+        // edges -> 35 / 77 / 135 / 489 walk rounds, 1.13 / 0.60 / 0.36 / 0.20 G records)
+        const uint64_t rmask = (uint64_t)std::max<int64_t>(0, knob(ctx, "dist.ruler_mask", comm.world > 2 ? 3 : 15));
         DevBuf<uint64_t> rbits(nwl + 1), bbits(nwl + 1);
-        if (n) {
-            hipLaunchKernelGGL(k_prep, dim3(s.grid(nwl * 64)), dim3(kBlk), 0, st, (const uint64_t *)post.p,
-                               (const uint64_t *)seed.p, kind.p, stt.p, nx.p, n, id_lo, rmask, rbits.p, bbits.p);
-            LAUNCH_OK();
-        }
-        nr = s.list_bits(rbits.p, rl);
-        nb = s.list_bits(bbits.p, bl);
+        run(nwl * 64, k_prep, post.p, seed.p, kind.p, stt.p, nx.p, n, id_lo, rmask, rbits.p, bbits.p);
+        pl.nr = list_bits(rbits.p, pl.rl, nwl);
+        pl.nb = list_bits(bbits.p, pl.bl, nwl);
     }
-    verbose_mark(ctx, "shard_cf.peel_prep");
-    uint64_t walk_rounds = 0;
-    // (round 6) the walk's tail in fixed blocks of dist.walk_block records (default 2^15; 0: every
-    // round routed, round 5's form)
-    const uint64_t walkP = (uint64_t)std::max<int64_t>(0, knob(ctx, "dist.walk_block", 1 << 15));
-    const bool walk_fixed = walkP > 0;
-    {
-        DevBuf<uint64_t> w(2 * (nr ? nr : 1));
-        if (nr) {
-            hipLaunchKernelGGL(k_walk_init, dim3(s.grid(nr)), dim3(kBlk), 0, st, (const uint64_t *)rl.p, nr,
-                               (const uint64_t *)nx.p, id_lo, w.p);
-            LAUNCH_OK();
+
+    // The walk's tail in fixed blocks of P records: every rank's records in flight fit one block
+    // (they never multiply), so the rounds run back to back on the device, one queued all-to-all
+    // each, checked once per batch of dist.walk_batch rounds (an empty round changes nothing).
+    // w: this rank's m records {ruler, edge}. Returns the rounds run.
+    uint64_t walk_tail_fixed(const uint64_t *w, uint64_t m, uint64_t P) {
+        const int N = comm.world, R = comm.rank;
+        const uint64_t bs = 1 + 2 * P;
+        DevBuf<uint64_t> send((uint64_t)N * bs), recv((uint64_t)N * bs), sb[2];
+        sb[0].alloc(bs);
+        sb[1].alloc(bs);
+        DevBuf<unsigned long long> tot(1);
+        run_at(dim3(1), dim3(kBlk), k_blk_zero, recv.p, N, bs, nullptr);
+        run(2 * m + 1, k_walk_fx_seed, w, m, sb[0].p);
+        const dim3 gw(grid(P) / (unsigned)N + 1, (unsigned)N);  // (blockIdx.y: the source rank)
+        const int K = (int)std::max<int64_t>(1, knob(ctx, "dist.walk_batch", 8));
+        uint64_t t = 0;
+        for (bool done = false; !done;) {
+            for (int b = 0; b < K; ++b, ++t) {
+                run_at(dim3(1), dim3(kBlk), k_blk_zero, send.p, N, bs, sb[(t + 1) & 1].p);
+                run_at(gw, dim3(kBlk), k_walk_fx, recv.p, sb[t & 1].p, R, P, kind.p, nx.p, o, send.p, sb[(t + 1) & 1].p,
+                       (int)merge_known);
+                comm.alltoall_fixed(send.p, 8 * bs, recv.p);
+            }
+            run_at(dim3(1), dim3(64), k_walk_fx_count, send.p, N, R, P, sb[t & 1].p, tot.p);
+            done = sum(read_u64(ctx, tot.p)) == 0;  // the batch's last round put nothing out
         }
-        uint64_t m = nr;
-        for (;; ++walk_rounds) {
+        return t;
+    }
+    // every ruler walks its chain, a routed exchange per round; dist.walk_block (records, default
+    // 2^15; 0: every round routed): once all records in flight fit one block, walk_tail_fixed
+    void peel_walk(Peel &pl) {
+        const uint64_t walkP = (uint64_t)std::max<int64_t>(0, knob(ctx, "dist.walk_block", 1 << 15));
+        DevBuf<uint64_t> w(2 * (pl.nr ? pl.nr : 1));
+        run(pl.nr, k_walk_init, pl.rl.p, pl.nr, nx.p, id_lo, w.p);
+        uint64_t m = pl.nr;
+        for (;; ++pl.walk_rounds) {
             DevBuf<uint64_t> o2(2 * (m ? m : 1));
             DevBuf<uint8_t> dest(m ? m : 1);
-            if (m) {
-                hipLaunchKernelGGL(k_walk, dim3(s.grid(m)), dim3(kBlk), 0, st, (const uint64_t *)w.p, m,
-                                   (const uint8_t *)kind.p, nx.p, s.o, o2.p, dest.p, (int)win_ranges);
-                LAUNCH_OK();
-            }
+            run(m, k_walk, w.p, m, kind.p, nx.p, o, o2.p, dest.p, (int)merge_known);
             Routed r;
-            s.rt.send(o2.p, 2, dest.p, m, r, false);
+            rt.send(o2.p, 2, dest.p, m, r, false);
             if (!r.total) break;
             w = std::move(r.in);
             m = r.n_in;
-            // (round 6) the tail: once every rank's records in flight fit one block (they never
-            // multiply), the rounds run in fixed blocks back to back on the device, one queued
-            // all-to-all each, checked once per batch (an empty round changes nothing)
-            if (walk_fixed && r.total <= walkP) {
-                const int N = comm.world, R = comm.rank;
-                const uint64_t P = walkP, bs = 1 + 2 * P;
-                DevBuf<uint64_t> send((uint64_t)N * bs), recv((uint64_t)N * bs), sb[2];
-                sb[0].alloc(bs);
-                sb[1].alloc(bs);
-                DevBuf<unsigned long long> tot(1);
-                hipLaunchKernelGGL(k_blk_zero, dim3(1), dim3(kBlk), 0, st, recv.p, N, bs, (uint64_t *)nullptr);
-                LAUNCH_OK();
-                hipLaunchKernelGGL(k_walk_fx_seed, dim3(s.grid(2 * m + 1)), dim3(kBlk), 0, st, (const uint64_t *)w.p, m,
-                                   sb[0].p);
-                LAUNCH_OK();
-                const unsigned gy = s.grid(P) / (unsigned)N + 1;
-                const int K = (int)std::max<int64_t>(1, knob(ctx, "dist.walk_batch", 8));
-                int t = 0;
-                for (bool done = false; !done;) {
-                    for (int b = 0; b < K; ++b, ++t, ++walk_rounds) {
-                        hipLaunchKernelGGL(k_blk_zero, dim3(1), dim3(kBlk), 0, st, send.p, N, bs, sb[(t + 1) & 1].p);
-                        LAUNCH_OK();
-                        hipLaunchKernelGGL(k_walk_fx, dim3(gy, (unsigned)N), dim3(kBlk), 0, st, (const uint64_t *)recv.p,
-                                           (const uint64_t *)sb[t & 1].p, R, P, (const uint8_t *)kind.p, nx.p, s.o, send.p,
-                                           sb[(t + 1) & 1].p, (int)win_ranges);
-                        LAUNCH_OK();
-                        comm.alltoall_fixed(send.p, 8 * bs, recv.p);
-                    }
-                    hipLaunchKernelGGL(k_walk_fx_count, dim3(1), dim3(64), 0, st, (const uint64_t *)send.p, N, R, P,
-                                       (const uint64_t *)sb[t & 1].p, tot.p);
-                    LAUNCH_OK();
-                    done = s.sum(read_u64(ctx, tot.p)) == 0;  // the batch's last round put nothing out
-                }
+            if (walkP && r.total <= walkP) {
+                pl.walk_rounds += walk_tail_fixed(w.p, m, walkP);
                 break;
             }
         }
     }
-    verbose_mark(ctx, "shard_cf.peel_walk");
+
     // pointer jumping over the rulers still pointing at a ruler
-    uint64_t jump_rounds = 0;
-    {
+    void peel_jumps(Peel &pl) {
+        const uint64_t nr = pl.nr;
         DevBuf<uint64_t> al;
         DevBuf<uint8_t> keep(nr + 1);
         uint64_t na = 0;
         if (nr) {
-            hipLaunchKernelGGL(k_active_rulers, dim3(s.grid(nr)), dim3(kBlk), 0, st, (const uint64_t *)rl.p, nr,
-                               (const uint64_t *)nx.p, keep.p);
-            LAUNCH_OK();
+            run(nr, k_active_rulers, pl.rl.p, nr, nx.p, keep.p);
             al.alloc(nr);
-            na = s.select(rl.p, keep.p, nr, al.p);
+            na = select(pl.rl.p, keep.p, nr, al.p);
         }
-        const uint64_t total_rulers = s.sum(nr);
+        const uint64_t total_rulers = sum(nr);
         int bound = 2;
         while ((1ULL << bound) < total_rulers + 1) ++bound;
         bound += 1;
-        for (; jump_rounds < (uint64_t)bound; ++jump_rounds) {
+        for (; pl.jump_rounds < (uint64_t)bound; ++pl.jump_rounds) {
             DevBuf<uint64_t> q(na ? na : 1);
             DevBuf<uint8_t> dest(na ? na : 1);
-            if (na) {
-                hipLaunchKernelGGL(k_jump_req, dim3(s.grid(na)), dim3(kBlk), 0, st, (const uint64_t *)al.p, na,
-                                   (const uint64_t *)nx.p, s.o, q.p, dest.p);
-                LAUNCH_OK();
-            }
+            run(na, k_jump_req, al.p, na, nx.p, o, q.p, dest.p);
+            // (spelled out, not round_trip: the count exchange also carries every rank's active
+            // rulers, and a round that carried nothing on any rank ends the loop before its reply)
             Routed r;
-            uint64_t active_all = 0;  // every rank's active rulers (round 5: a sum of its own first)
-            s.rt.send(q.p, 1, dest.p, na, r, true, na, &active_all);
-            if (active_all == 0) break;  // (the round carried nothing on any rank)
+            uint64_t active_all = 0;
+            rt.send(q.p, 1, dest.p, na, r, true, na, &active_all);
+            if (active_all == 0) break;
             DevBuf<uint64_t> ans(r.n_in + 1);
-            if (r.n_in) {
-                hipLaunchKernelGGL(k_jump_ans, dim3(s.grid(r.n_in)), dim3(kBlk), 0, st, (const uint64_t *)r.in.p, r.n_in,
-                                   (const uint64_t *)nx.p, id_lo, ans.p);
-                LAUNCH_OK();
-            }
-            s.rt.reply(r, ans.p, 1, q.p);
+            run(r.n_in, k_jump_ans, r.in.p, r.n_in, nx.p, id_lo, ans.p);
+            rt.reply(r, ans.p, 1, q.p);
             if (na) {
-                hipLaunchKernelGGL(k_jump_apply, dim3(s.grid(na)), dim3(kBlk), 0, st, (const uint64_t *)al.p, na,
-                                   (const uint64_t *)q.p, nx.p, keep.p);
-                LAUNCH_OK();
+                run(na, k_jump_apply, al.p, na, q.p, nx.p, keep.p);
                 DevBuf<uint64_t> al2(na);
-                na = s.select(al.p, keep.p, na, al2.p);
+                na = select(al.p, keep.p, na, al2.p);
                 al = std::move(al2);
             }
         }
         // still pointing at a ruler after the bound: a unary cycle (or a chain into one) survives
-        if (na) {
-            hipLaunchKernelGGL(k_jump_cycle, dim3(s.grid(na)), dim3(kBlk), 0, st, (const uint64_t *)al.p, na, nx.p);
-            LAUNCH_OK();
-        }
+        run(na, k_jump_cycle, al.p, na, nx.p);
     }
-    verbose_mark(ctx, "shard_cf.peel_jumps");
+
     // branch successors' references (two lookups: the successor, then a claiming ruler's terminal)
-    DevBuf<uint64_t> ref(4 * (nb ? nb : 1));  // per branch slot: its successor's reference, kPad unused
-    if (nb) {
-        hipLaunchKernelGGL(k_fill, dim3(s.grid(4 * nb)), dim3(kBlk), 0, st, ref.p, 4 * nb, kPad);
-        LAUNCH_OK();
-    }
-    {
+    void peel_bref(Peel &pl) {
+        const uint64_t nb = pl.nb;
+        pl.ref.alloc(4 * (nb ? nb : 1));
+        run(4 * nb, k_fill, pl.ref.p, 4 * nb, kPad);
         DevBuf<uint64_t> q(4 * nb + 1);
         DevBuf<uint8_t> dest(4 * nb + 1);
-        if (nb) {
-            hipLaunchKernelGGL(k_bref_req, dim3(s.grid(nb)), dim3(kBlk), 0, st, (const uint64_t *)bl.p, nb,
-                               (const uint8_t *)kind.p, (const uint64_t *)g->out_info.p, s.o, q.p, dest.p);
-            LAUNCH_OK();
-        }
-        Routed r;
-        s.rt.send(q.p, 1, dest.p, 4 * nb, r, true);
-        DevBuf<uint64_t> ans(r.n_in + 1);
-        if (r.n_in) {
-            hipLaunchKernelGGL(k_bref_ans, dim3(s.grid(r.n_in)), dim3(kBlk), 0, st, (const uint64_t *)r.in.p, r.n_in,
-                               (const uint8_t *)kind.p, (const uint64_t *)nx.p, id_lo, ans.p);
-            LAUNCH_OK();
-        }
-        s.rt.reply(r, ans.p, 1, ref.p);  // slots without a successor keep kPad
+        run(nb, k_bref_req, pl.bl.p, nb, kind.p, g->out_info.p, o, q.p, dest.p);
+        // (slots without a successor keep kPad)
+        rt.round_trip(q.p, dest.p, 4 * nb, pl.ref.p, [&](const uint64_t *in, uint64_t m, uint64_t *ans) {
+            run(m, k_bref_ans, in, m, kind.p, nx.p, id_lo, ans);
+        });
         // second step: a claiming ruler's terminal replaces kRef | ruler
-        if (nb) {
-            hipLaunchKernelGGL(k_bref_req2, dim3(s.grid(4 * nb)), dim3(kBlk), 0, st, (const uint64_t *)ref.p, 4 * nb, s.o,
-                               q.p, dest.p);
-            LAUNCH_OK();
-        }
-        Routed r2;
-        s.rt.send(q.p, 1, dest.p, 4 * nb, r2, true);
-        DevBuf<uint64_t> ans2(r2.n_in + 1);
-        if (r2.n_in) {
-            hipLaunchKernelGGL(k_jump_ans, dim3(s.grid(r2.n_in)), dim3(kBlk), 0, st, (const uint64_t *)r2.in.p, r2.n_in,
-                               (const uint64_t *)nx.p, id_lo, ans2.p);
-            LAUNCH_OK();
-        }
-        s.rt.reply(r2, ans2.p, 1, ref.p);
+        run(4 * nb, k_bref_req2, pl.ref.p, 4 * nb, o, q.p, dest.p);
+        rt.round_trip(q.p, dest.p, 4 * nb, pl.ref.p, [&](const uint64_t *in, uint64_t m, uint64_t *ans) {
+            run(m, k_jump_ans, in, m, nx.p, id_lo, ans);
+        });
     }
-    verbose_mark(ctx, "shard_cf.peel_bref");
-    // branch resolution rounds (until no branch changes on any rank)
-    uint64_t res_rounds = 0;
-    // (round 6) in fixed blocks, the rounds back to back on the device in batches (a round after
-    // one without a change changes nothing, so the batch's last round decides): one queued
-    // all-to-all each way per round and one host wait per batch, against a routed exchange, a
-    // reply and a sum (three host waits) per round. Blocks hold every slot of the rank with the
-    // most branches; above dist.res_block_mb (64 MB of blocks) the routed rounds stay.
-    const uint64_t nb_most = [&] {
-        uint64_t x = 0;
-        for (uint64_t v : comm.allgather_one(nb)) x = std::max(x, v);
-        return x;
-    }();
-    const uint64_t resP = 4 * nb_most;
-    const bool res_fixed = knob(ctx, "dist.res_fixed", 1) != 0 &&
-                           8 * (uint64_t)comm.world * (1 + resP) <= ((uint64_t)std::max<int64_t>(1, knob(ctx, "dist.res_block_mb", 64)) << 20);
-    if (res_fixed) {
+
+    // Branch resolution in fixed blocks of P slots per rank: the rounds run back to back on the
+    // device in batches of dist.res_batch (a round after one without a change changes nothing, so
+    // the batch's last round decides): one queued all-to-all each way per round and one host wait
+    // per batch
+    void resolve_fixed(Peel &pl, uint64_t P) {
         const int N = comm.world, R = comm.rank;
-        const uint64_t m = 4 * nb, P = resP;
+        const uint64_t nb = pl.nb, m = 4 * nb;
         DevBuf<uint64_t> q(m + 1), a(m + 1);
         DevBuf<uint8_t> dest(m + 1);
         DevBuf<uint32_t> pos(m + 1);
         DevBuf<uint64_t> send((uint64_t)N * (1 + P)), recv((uint64_t)N * (1 + P)), self_blk(1 + m);
         DevBuf<uint64_t> rsend((uint64_t)N * (1 + P)), rrecv((uint64_t)N * (1 + P)), rself(1 + m);
+        const dim3 ga(grid(std::max<uint64_t>(m, 1)) / (unsigned)N + 1, (unsigned)N);  // (blockIdx.y: the source rank)
         const int K = (int)std::max<int64_t>(1, knob(ctx, "dist.res_batch", 8));
         for (bool done = false; !done;) {
-            for (int b = 0; b < K; ++b, ++res_rounds) {
+            for (int b = 0; b < K; ++b, ++pl.res_rounds) {
                 HIP_OK(hipMemsetAsync(cnt.p + 7, 0, 8, st));
-                hipLaunchKernelGGL(k_bfs_zero, dim3(1), dim3(kBlk), 0, st, send.p, N, P, self_blk.p);
-                LAUNCH_OK();
-                if (nb) {
-                    hipLaunchKernelGGL(k_res_req, dim3(s.grid(nb)), dim3(kBlk), 0, st, (const uint64_t *)bl.p,
-                                       (const uint64_t *)ref.p, nb, stt.p, s.o, q.p, dest.p, cnt.p + 7);
-                    LAUNCH_OK();
-                    hipLaunchKernelGGL(k_fx_post, dim3(s.grid(m)), dim3(kBlk), 0, st, (const uint64_t *)q.p,
-                                       (const uint8_t *)dest.p, m, R, send.p, P, self_blk.p, pos.p);
-                    LAUNCH_OK();
-                }
+                run_at(dim3(1), dim3(kBlk), k_blk_zero, send.p, N, 1 + P, self_blk.p);
+                run(nb, k_res_req, pl.bl.p, pl.ref.p, nb, stt.p, o, q.p, dest.p, cnt.p + 7);
+                run(m, k_fx_post, q.p, dest.p, m, R, send.p, P, self_blk.p, pos.p);
                 comm.alltoall_fixed(send.p, 8 * (1 + P), recv.p);
-                hipLaunchKernelGGL(k_fx_st_ans, dim3(s.grid(std::max<uint64_t>(m, 1)) / (unsigned)N + 1, (unsigned)N),
-                                   dim3(kBlk), 0, st, (const uint64_t *)recv.p, (const uint64_t *)self_blk.p, R, P,
-                                   (const uint8_t *)stt.p, id_lo, rsend.p, rself.p);
-                LAUNCH_OK();
+                run_at(ga, dim3(kBlk), k_fx_st_ans, recv.p, self_blk.p, R, P, stt.p, id_lo, rsend.p, rself.p);
                 comm.alltoall_fixed(rsend.p, 8 * (1 + P), rrecv.p);
-                if (nb) {
-                    hipLaunchKernelGGL(k_fx_gather, dim3(s.grid(m)), dim3(kBlk), 0, st, (const uint8_t *)dest.p,
-                                       (const uint32_t *)pos.p, m, R, (const uint64_t *)rrecv.p, P,
-                                       (const uint64_t *)rself.p, a.p);
-                    LAUNCH_OK();
-                    hipLaunchKernelGGL(k_res_apply, dim3(s.grid(nb)), dim3(kBlk), 0, st, (const uint64_t *)bl.p, nb,
-                                       (const uint64_t *)a.p, (const uint8_t *)dest.p, stt.p, cnt.p + 7);
-                    LAUNCH_OK();
-                }
+                run(m, k_fx_gather, dest.p, pos.p, m, R, rrecv.p, P, rself.p, a.p);
+                run(nb, k_res_apply, pl.bl.p, nb, a.p, dest.p, stt.p, cnt.p + 7);
             }
-            const uint64_t ch = read_u64(ctx, cnt.p + 7);  // the batch's last round
-            done = s.sum(ch) == 0;
-        }
-    } else {
-        DevBuf<uint64_t> q(4 * nb + 1);
-        DevBuf<uint8_t> dest(4 * nb + 1);
-        for (;; ++res_rounds) {
-            HIP_OK(hipMemsetAsync(cnt.p + 7, 0, 8, st));
-            if (nb) {
-                hipLaunchKernelGGL(k_res_req, dim3(s.grid(nb)), dim3(kBlk), 0, st, (const uint64_t *)bl.p,
-                                   (const uint64_t *)ref.p, nb, stt.p, s.o, q.p, dest.p, cnt.p + 7);
-                LAUNCH_OK();
-            }
-            Routed r;
-            s.rt.send(q.p, 1, dest.p, 4 * nb, r, true);
-            DevBuf<uint64_t> ans(r.n_in + 1);
-            if (r.n_in) {
-                hipLaunchKernelGGL(k_st_ans, dim3(s.grid(r.n_in)), dim3(kBlk), 0, st, (const uint64_t *)r.in.p, r.n_in,
-                                   (const uint8_t *)stt.p, id_lo, ans.p);
-                LAUNCH_OK();
-            }
-            s.rt.reply(r, ans.p, 1, q.p);
-            if (nb) {
-                hipLaunchKernelGGL(k_res_apply, dim3(s.grid(nb)), dim3(kBlk), 0, st, (const uint64_t *)bl.p, nb,
-                                   (const uint64_t *)q.p, (const uint8_t *)dest.p, stt.p, cnt.p + 7);
-                LAUNCH_OK();
-            }
-            const uint64_t ch = nb ? read_u64(ctx, cnt.p + 7) : 0;
-            if (s.sum(ch) == 0) break;
+            done = sum(read_u64(ctx, cnt.p + 7)) == 0;  // the batch's last round
         }
     }
-    verbose_mark(ctx, "shard_cf.peel_resolution");
-    // removal: resolved non-unary edges, rulers whose terminal went, and the chains they claimed
-    uint64_t n_rm_rulers = 0;
-    {
-        if (nwl) {
-            hipLaunchKernelGGL(k_rm_nonunary, dim3(s.grid(nwl * 64)), dim3(kBlk), 0, st, (const uint64_t *)post.p,
-                               (const uint8_t *)kind.p, (const uint8_t *)stt.p, n, g->valid.p);
-            LAUNCH_OK();
+    // the same by routed rounds (dist.res_fixed=0, or blocks above dist.res_block_mb): a routed
+    // exchange, a reply and a sum per round
+    void resolve_routed(Peel &pl) {
+        const uint64_t nb = pl.nb;
+        DevBuf<uint64_t> q(4 * nb + 1);
+        DevBuf<uint8_t> dest(4 * nb + 1);
+        for (;; ++pl.res_rounds) {
+            HIP_OK(hipMemsetAsync(cnt.p + 7, 0, 8, st));
+            run(nb, k_res_req, pl.bl.p, pl.ref.p, nb, stt.p, o, q.p, dest.p, cnt.p + 7);
+            rt.round_trip(q.p, dest.p, 4 * nb, q.p, [&](const uint64_t *in, uint64_t m, uint64_t *ans) {
+                run(m, k_st_ans, in, m, stt.p, id_lo, ans);
+            });
+            run(nb, k_res_apply, pl.bl.p, nb, q.p, dest.p, stt.p, cnt.p + 7);
+            const uint64_t ch = nb ? read_u64(ctx, cnt.p + 7) : 0;
+            if (sum(ch) == 0) break;
         }
+    }
+    // branch resolution rounds, until no branch changes on any rank
+    void peel_resolution(Peel &pl) {
+        // fixed blocks hold every slot of the rank with the most branches; above dist.res_block_mb
+        // (MB of blocks, default 64) the routed rounds stay
+        uint64_t nb_most = 0;
+        for (uint64_t v : comm.allgather_one(pl.nb)) nb_most = std::max(nb_most, v);
+        const uint64_t P = 4 * nb_most;
+        // TODO(ADVICE.md item 2): resolve_fixed allocates four such block sets; the gate counts one
+        const bool fixed = knob(ctx, "dist.res_fixed", 1) != 0 &&
+                           8 * (uint64_t)comm.world * (1 + P) <= ((uint64_t)std::max<int64_t>(1, knob(ctx, "dist.res_block_mb", 64)) << 20);
+        if (fixed) resolve_fixed(pl, P);
+        else resolve_routed(pl);
+    }
+
+    // removal: resolved non-unary edges, rulers whose terminal went, and the chains they claimed
+    void peel_removal(Peel &pl) {
+        const uint64_t nr = pl.nr;
+        run(nwl * 64, k_rm_nonunary, post.p, kind.p, stt.p, n, g->valid.p);
         DevBuf<uint64_t> q(nr + 1);
         DevBuf<uint8_t> dest(nr + 1);
-        if (nr) {
-            hipLaunchKernelGGL(k_term_req, dim3(s.grid(nr)), dim3(kBlk), 0, st, (const uint64_t *)rl.p, nr,
-                               (const uint64_t *)nx.p, s.o, q.p, dest.p);
-            LAUNCH_OK();
-        }
-        Routed r;
-        s.rt.send(q.p, 1, dest.p, nr, r, true);
-        DevBuf<uint64_t> ans(r.n_in + 1);
-        if (r.n_in) {
-            hipLaunchKernelGGL(k_st_ans, dim3(s.grid(r.n_in)), dim3(kBlk), 0, st, (const uint64_t *)r.in.p, r.n_in,
-                               (const uint8_t *)stt.p, id_lo, ans.p);
-            LAUNCH_OK();
-        }
-        s.rt.reply(r, ans.p, 1, q.p);
+        run(nr, k_term_req, pl.rl.p, nr, nx.p, o, q.p, dest.p);
+        rt.round_trip(q.p, dest.p, nr, q.p, [&](const uint64_t *in, uint64_t m, uint64_t *ans) {
+            run(m, k_st_ans, in, m, stt.p, id_lo, ans);
+        });
         DevBuf<uint64_t> rm(nr + 1), gidr(nr + 1);
         DevBuf<uint8_t> flag(nr + 1);
         uint64_t nrm = 0;
         if (nr) {
-            hipLaunchKernelGGL(k_rm_rulers, dim3(s.grid(nr)), dim3(kBlk), 0, st, (const uint64_t *)rl.p, nr,
-                               (const uint64_t *)q.p, (const uint8_t *)dest.p, g->valid.p, id_lo, gidr.p, flag.p);
-            LAUNCH_OK();
-            nrm = s.select(gidr.p, flag.p, nr, rm.p);
+            run(nr, k_rm_rulers, pl.rl.p, nr, q.p, dest.p, g->valid.p, id_lo, gidr.p, flag.p);
+            nrm = select(gidr.p, flag.p, nr, rm.p);
         }
         const std::vector<uint64_t> per = comm.allgather_one(nrm);
         std::vector<uint64_t> bytes(comm.world);
-        for (int r2 = 0; r2 < comm.world; ++r2) n_rm_rulers += per[r2], bytes[r2] = 8 * per[r2];
-        if (n_rm_rulers) {
-            DevBuf<uint64_t> allrm(n_rm_rulers);
+        for (int r = 0; r < comm.world; ++r) pl.n_rm_rulers += per[r], bytes[r] = 8 * per[r];
+        if (pl.n_rm_rulers) {
+            DevBuf<uint64_t> allrm(pl.n_rm_rulers);
             HIP_OK(hipStreamSynchronize(st));
             comm.allgatherv_dev(rm.p, allrm.p, bytes.data());
-            const uint64_t cap = next_pow2(2 * n_rm_rulers + 16);
+            const uint64_t cap = next_pow2(2 * pl.n_rm_rulers + 16);
             DevBuf<uint64_t> tab(cap);
             HIP_OK(hipMemsetAsync(tab.p, 0xFF, tab.bytes(), st));
-            hipLaunchKernelGGL(k_set_build, dim3(s.grid(n_rm_rulers)), dim3(kBlk), 0, st, (const uint64_t *)allrm.p,
-                               n_rm_rulers, tab.p, cap);
-            LAUNCH_OK();
-            if (nwl) {
-                hipLaunchKernelGGL(k_rm_chains, dim3(s.grid(nwl * 64)), dim3(kBlk), 0, st, (const uint64_t *)post.p,
-                                   (const uint8_t *)kind.p, (const uint64_t *)nx.p, n, (const uint64_t *)tab.p, cap,
-                                   g->valid.p);
-                LAUNCH_OK();
-            }
+            run(pl.n_rm_rulers, k_set_build, allrm.p, pl.n_rm_rulers, tab.p, cap);
+            run(nwl * 64, k_rm_chains, post.p, kind.p, nx.p, n, tab.p, cap, g->valid.p);
         }
         HIP_OK(hipStreamSynchronize(st));
     }
-    if (verbose())
-        fprintf(stderr,
-                "[mcaat] shard %d peel: %llu rulers, %llu branches; walk %llu rounds, jumps %llu, resolution %llu; "
-                "%llu removed rulers\n",
-                comm.rank, (unsigned long long)nr, (unsigned long long)nb, (unsigned long long)walk_rounds,
-                (unsigned long long)jump_rounds, (unsigned long long)res_rounds, (unsigned long long)n_rm_rulers);
-    verbose_mark(ctx, "shard_cf.peel_removal");
-    kind.release();
-    stt.release();
-    nx.release();
-    rl.release();
-    bl.release();
-    ref.release();
-    seed.release();
-    timer.mark("peel");
-    xr("peel");
 
-    // 4-5. valid count; the candidates still valid, ascending on every rank
-    HIP_OK(hipMemsetAsync(cnt.p, 0, 16, st));
-    if (nwl) {
-        hipLaunchKernelGGL(k_popc, dim3(s.grid(nwl)), dim3(kBlk), 0, st, (const uint64_t *)g->valid.p, nwl, cnt.p);
-        LAUNCH_OK();
+    // rulers, walks, pointer jumping, branch references and resolution, removal
+    void peel() {
+        Peel pl;
+        peel_prep(pl);
+        verbose_mark(ctx, "shard_cf.peel_prep");
+        peel_walk(pl);
+        verbose_mark(ctx, "shard_cf.peel_walk");
+        peel_jumps(pl);
+        verbose_mark(ctx, "shard_cf.peel_jumps");
+        peel_bref(pl);
+        verbose_mark(ctx, "shard_cf.peel_bref");
+        peel_resolution(pl);
+        verbose_mark(ctx, "shard_cf.peel_resolution");
+        peel_removal(pl);
+        if (verbose())
+            fprintf(stderr,
+                    "[mcaat] shard %d peel: %llu rulers, %llu branches; walk %llu rounds, jumps %llu, resolution %llu; "
+                    "%llu removed rulers\n",
+                    comm.rank, (unsigned long long)pl.nr, (unsigned long long)pl.nb, (unsigned long long)pl.walk_rounds,
+                    (unsigned long long)pl.jump_rounds, (unsigned long long)pl.res_rounds, (unsigned long long)pl.n_rm_rulers);
+        verbose_mark(ctx, "shard_cf.peel_removal");
+        // the per-edge marks end with the peel (before the recount allocates)
+        kind.release();
+        stt.release();
+        nx.release();
+        seed.release();
     }
-    out->stats[2] = s.sum(read_u64(ctx, cnt.p));
-    std::vector<uint64_t> cand_mine;  // the candidates still valid, ascending ids
-    {
-        if (nwl) {
-            hipLaunchKernelGGL(k_and_words, dim3(s.grid(nwl)), dim3(kBlk), 0, st, cbits.p, (const uint64_t *)g->valid.p, nwl);
-            LAUNCH_OK();
-        }
+
+    // ---------------- stage: recount
+    // the valid count; the candidates still valid, ascending
+    void recount() {
+        HIP_OK(hipMemsetAsync(cnt.p, 0, 16, st));
+        run(nwl, k_popc, g->valid.p, nwl, cnt.p);
+        out->stats[2] = sum(read_u64(ctx, cnt.p));
+        run(nwl, k_and_words, cbits.p, g->valid.p, nwl);
         DevBuf<uint64_t> cl;
-        const uint64_t nk = s.list_bits(cbits.p, cl);
+        const uint64_t nk = list_bits(cbits.p, cl, nwl);
         cand_mine.resize(nk);
         if (nk) d2h(ctx, cand_mine.data(), cl.p, 8 * nk);
         for (auto &x : cand_mine) x += id_lo;
+        cbits.release();
+        post.release();
     }
-    cbits.release();
-    post.release();
-    timer.mark("recount");
-    xr("recount");
 
-    // 6. search regions: groups of the (k-1)-suffix (whole nodes' out-edges and in-groups)
-    DevBuf<uint64_t> gs(nwl + 1), reg(nwl + 1), seen(nwl + 1);
-    HIP_OK(hipMemsetAsync(gs.p, 0, gs.bytes(), st));
-    if (nwl) {
-        hipLaunchKernelGGL(k_gstart, dim3(s.grid(nwl * 64)), dim3(kBlk), 0, st, (const uint64_t *)g->key.p, n, gs.p);
-        LAUNCH_OK();
+    // ---------------- stage: candidates (the DepthLevelSearch region)
+    // search regions are made of groups of the (k-1)-suffix (whole nodes' out-edges and
+    // in-groups): the valid edges within cycle_max_length + 1 hops of the candidates, gathered
+    // into a replica on every rank
+    void dls_region() {
+        gs.alloc(nwl + 1);
+        reg.alloc(nwl + 1);
+        seen.alloc(nwl + 1);
+        HIP_OK(hipMemsetAsync(gs.p, 0, gs.bytes(), st));
+        run(nwl * 64, k_gstart, g->key.p, n, gs.p);
+        region_bfs(cand_mine, radius, false);
+        verbose_mark(ctx, "shard_cf.dls_region_bfs");
+        rn = gather_region(&rg);
+        cand_all = comm.allgather_vec(cand_mine);
+        std::sort(cand_all.begin(), cand_all.end());
     }
-    const uint64_t radius = (uint64_t)p.cycle_max_length + 1;
-    // (round 6) the region BFS hops run back to back on the device (ShardCf::bfs_dev);
-    // dist.bfs_sync=1: round 5's form, one routed exchange with host waits per hop
-    const bool bfs_sync = knob(ctx, "dist.bfs_sync", 0) != 0;
-    auto forward_region = [&](const std::vector<uint64_t> &starts_mine) {
-        if (!bfs_sync) {
-            s.bfs_dev(starts_mine, radius, false, gs.p, reg.p, seen.p);
-            return;
+
+    // ---------------- stage: dls
+    // DepthLevelSearch on the replica; the passing candidates in buckets by ceil(log2 mult)
+    // (cycle_finder.cpp:414), descending, ascending ids within: FindCycle's starts
+    void dls_search() {
+        if (verbose())
+            fprintf(stderr, "[mcaat] shard %d: %zu candidates, DLS region %llu edges\n", comm.rank, cand_all.size(),
+                    (unsigned long long)rn);
+        ctx->kstats["shard_dls_region_edges"].launches = rn;
+        verbose_mark(ctx, "shard_cf.dls_begin");
+        const std::vector<uint64_t> cand_c = to_compact(rg, rn, cand_all);
+        verbose_mark(ctx, "shard_cf.dls_compact_ids");
+        std::vector<uint64_t> pass_c = cf_depth_level_search(&rg, cand_c, p.cycle_max_length, &comm);
+        verbose_mark(ctx, "shard_cf.dls_search");
+        std::map<int, std::vector<uint64_t>, std::greater<int>> chunks;
+        if (!pass_c.empty()) {
+            const uint64_t m = pass_c.size();
+            DevBuf<uint64_t> dc(m);
+            DevBuf<uint16_t> dm(m);
+            h2d(ctx, dc.p, pass_c.data(), 8 * m);
+            run(m, k_mult_of, rg.mult.p, dc.p, m, dm.p);
+            std::vector<uint16_t> hm(m);
+            d2h(ctx, hm.data(), dm.p, 2 * m);
+            const std::vector<uint64_t> ids = to_global(rg, rn, dc.p, m);
+            for (uint64_t i = 0; i < m; ++i) chunks[(int)std::ceil(std::log2(double(hm[i])))].push_back(ids[i]);
         }
-        HIP_OK(hipMemsetAsync(reg.p, 0, reg.bytes(), st));
-        HIP_OK(hipMemsetAsync(seen.p, 0, seen.bytes(), st));
-        const uint64_t m = starts_mine.size();
-        DevBuf<uint64_t> ids(m + 1), front(m + 1);
-        if (m) {
-            h2d(ctx, ids.p, starts_mine.data(), 8 * m);
-            hipLaunchKernelGGL(k_bfs_seed, dim3(s.grid(m)), dim3(kBlk), 0, st, (const uint64_t *)ids.p, m, id_lo, n,
-                               (const uint64_t *)gs.p, reg.p, seen.p, front.p);
-            LAUNCH_OK();
-        }
-        s.bfs(front, m, radius, false, gs.p, reg.p, seen.p);
-    };
-    // DepthLevelSearch region: valid edges within cycle_max_length + 1 hops of the candidates
-    forward_region(cand_mine);
-    verbose_mark(ctx, "shard_cf.dls_region_bfs");
-    mcaat_graph rg;
-    const uint64_t rn = s.gather_region(reg.p, &rg);
-    const std::vector<uint64_t> cand_all = [&] {
-        std::vector<uint64_t> a = comm.allgather_vec(cand_mine);
-        std::sort(a.begin(), a.end());
-        return a;
-    }();
-    timer.mark("candidates");
-    xr("candidates");
-    if (verbose())
-        fprintf(stderr, "[mcaat] shard %d: %zu candidates, DLS region %llu edges\n", comm.rank, cand_all.size(),
-                (unsigned long long)rn);
-    ctx->kstats["shard_dls_region_edges"].launches = rn;
-    verbose_mark(ctx, "shard_cf.dls_begin");
-    const std::vector<uint64_t> cand_c = s.to_compact(rg, rn, cand_all);
-    verbose_mark(ctx, "shard_cf.dls_compact_ids");
-    std::vector<uint64_t> pass_c = cf_depth_level_search(&rg, cand_c, p.cycle_max_length, &comm);
-    verbose_mark(ctx, "shard_cf.dls_search");
-    // buckets by ceil(log2 mult) (cycle_finder.cpp:414), descending; ascending ids within
-    std::map<int, std::vector<uint64_t>, std::greater<int>> chunks;
-    if (!pass_c.empty()) {
-        const uint64_t m = pass_c.size();
-        DevBuf<uint64_t> dc(m);
-        DevBuf<uint16_t> dm(m);
-        h2d(ctx, dc.p, pass_c.data(), 8 * m);
-        hipLaunchKernelGGL(k_mult_of, dim3(s.grid(m)), dim3(kBlk), 0, st, (const uint16_t *)rg.mult.p,
-                           (const uint64_t *)dc.p, m, dm.p);
-        LAUNCH_OK();
-        std::vector<uint16_t> hm(m);
-        d2h(ctx, hm.data(), dm.p, 2 * m);
-        const std::vector<uint64_t> ids = s.to_global(rg, rn, dc.p, m);
-        for (uint64_t i = 0; i < m; ++i) chunks[(int)std::ceil(std::log2(double(hm[i])))].push_back(ids[i]);
+        for (auto &kv : chunks)
+            for (uint64_t id : kv.second) {
+                out->cand_ids.push_back(id);
+                out->cand_bucket.push_back(kv.first);
+                starts.push_back(id);
+            }
+        out->stats[4] = out->cand_ids.size();
+        verbose_mark(ctx, "shard_cf.dls_buckets");
     }
-    std::vector<uint64_t> starts;
-    for (auto &kv : chunks)
-        for (uint64_t id : kv.second) {
-            out->cand_ids.push_back(id);
-            out->cand_bucket.push_back(kv.first);
-            starts.push_back(id);
-        }
-    out->stats[4] = out->cand_ids.size();
-    verbose_mark(ctx, "shard_cf.dls_buckets");
     // FindCycle's forward reach (cycle_max_length + 1 hops from the starts) lies inside the
-    // DepthLevelSearch region (the starts are candidates): found on the replica, no exchange
-    std::vector<uint64_t> fwd;  // its edge ids, ascending
-    {
-        const std::vector<uint64_t> sc = s.to_compact(rg, rn, starts);
-        const uint64_t nwr = mcaat_graph::bitmap_words(rg.D);
+    // DepthLevelSearch region (the starts are candidates): found on the replica, no exchange.
+    // hops[h] is the frontier size of hop h, in device memory; by default the hops run back to
+    // back (ping-pong frontiers of the replica's size, one host wait after the last),
+    // dist.bfs_sync=1 reads each size back and sizes the next frontier by it
+    void fc_reach() {
+        const std::vector<uint64_t> sc = to_compact(rg, rn, starts);
+        const uint64_t nwr = mcaat_graph::bitmap_words(rg.D), nf = sc.size();
         DevBuf<uint64_t> rseen(nwr);
         HIP_OK(hipMemsetAsync(rseen.p, 0, rseen.bytes(), st));
-        const uint64_t nf = sc.size();
-        if (nf && knob(ctx, "dist.bfs_sync", 0) == 0) {
-            // (round 6) the hops back to back on the device: ping-pong frontiers of the replica's
-            // size, per-hop counts in device memory (one host wait after the last hop instead of
-            // one per hop: C3 at one rank, the DLS stage's 78 waits)
-            DevBuf<uint64_t> fr[2];
-            fr[0].alloc(rg.D + 1);
-            fr[1].alloc(rg.D + 1);
-            DevBuf<unsigned long long> cnt(radius + 1);
-            HIP_OK(hipMemsetAsync(cnt.p, 0, cnt.bytes(), st));
-            h2d(ctx, fr[0].p, sc.data(), 8 * nf);
-            h2d(ctx, cnt.p, &nf, 8);
-            hipLaunchKernelGGL(k_set_ids, dim3(s.grid(nf)), dim3(kBlk), 0, st, (const uint64_t *)fr[0].p, nf, rseen.p);
-            LAUNCH_OK();
-            const unsigned gcap = s.grid(rg.D);
-            for (uint64_t h = 0; h < radius; ++h) {
-                hipLaunchKernelGGL(k_cbfs_dev, dim3(gcap), dim3(kBlk), 0, st, rg.view(), (const uint64_t *)fr[h & 1].p,
-                                   (const unsigned long long *)(cnt.p + h), rseen.p, fr[(h + 1) & 1].p, cnt.p + h + 1);
-                LAUNCH_OK();
-            }
-            HIP_OK(hipStreamSynchronize(st));
-        } else if (nf) {  // dist.bfs_sync=1: round 5's form, the frontier size read after every hop
-            DevBuf<uint64_t> front(nf + 1);
-            DevBuf<unsigned long long> nn(1);
-            uint64_t m = nf;
+        if (nf) {
+            DevBuf<unsigned long long> hops(radius + 1);
+            HIP_OK(hipMemsetAsync(hops.p, 0, hops.bytes(), st));
+            h2d(ctx, hops.p, &nf, 8);
+            DevBuf<uint64_t> front(bfs_sync ? nf + 1 : rg.D + 1), next;
             h2d(ctx, front.p, sc.data(), 8 * nf);
-            hipLaunchKernelGGL(k_set_ids, dim3(s.grid(nf)), dim3(kBlk), 0, st, (const uint64_t *)front.p, nf, rseen.p);
-            LAUNCH_OK();
-            for (uint64_t h = 0; h < radius && m; ++h) {
-                DevBuf<uint64_t> next(4 * m);
-                HIP_OK(hipMemsetAsync(nn.p, 0, 8, st));
-                hipLaunchKernelGGL(k_cbfs, dim3(s.grid(m)), dim3(kBlk), 0, st, rg.view(), (const uint64_t *)front.p, m,
-                                   rseen.p, next.p, nn.p);
-                LAUNCH_OK();
-                m = read_u64(ctx, nn.p);
-                front = std::move(next);
+            run(nf, k_set_ids, front.p, nf, rseen.p);
+            if (!bfs_sync) {
+                next.alloc(rg.D + 1);
+                for (uint64_t h = 0; h < radius; ++h, std::swap(front, next))
+                    run(rg.D, k_cbfs, rg.view(), front.p, hops.p + h, rseen.p, next.p, hops.p + h + 1);
+                HIP_OK(hipStreamSynchronize(st));
+            } else {
+                uint64_t m = nf;
+                for (uint64_t h = 0; h < radius && m; ++h, std::swap(front, next)) {
+                    next.alloc(4 * m);
+                    run(m, k_cbfs, rg.view(), front.p, hops.p + h, rseen.p, next.p, hops.p + h + 1);
+                    m = read_u64(ctx, hops.p + h + 1);
+                }
             }
         }
         // the reached compact ids, ascending, as edge ids (ascending too); the null group's
         // positions past the region's edges come last and are dropped
         DevBuf<uint64_t> rl;
-        const uint64_t nl = s.list_bits(rseen.p, rl, nwr);
-        fwd = s.to_global(rg, rn, rl.p, nl);
+        const uint64_t nl = list_bits(rseen.p, rl, nwr);
+        fwd = to_global(rg, rn, rl.p, nl);
         while (!fwd.empty() && fwd.back() == ~0ULL) fwd.pop_back();
+        verbose_mark(ctx, "shard_cf.fc_reach");
+        rg = mcaat_graph{};
     }
-    verbose_mark(ctx, "shard_cf.fc_reach");
-    rg = mcaat_graph{};
-    timer.mark("dls");
-    xr("dls");
 
-    // 7. FindCycle region: the forward reach found on the DepthLevelSearch replica above, then
-    // cycle_max_length + 1 hops backward from every edge of it (the lock relaxation's reach)
-    {
+    // ---------------- stage: find_cycle
+    // FindCycle's region: the forward reach, then cycle_max_length + 1 hops backward from every
+    // edge of it (the lock relaxation's reach); returns its edges
+    uint64_t fc_region(mcaat_graph *fg) {
         // this rank's edges of the forward reach: their groups, and the sources of the backward BFS
         const auto a = std::lower_bound(fwd.begin(), fwd.end(), id_lo), b = std::lower_bound(fwd.begin(), fwd.end(), id_lo + n);
-        const std::vector<uint64_t> sm(a, b);
-        if (!bfs_sync) s.bfs_dev(sm, radius, true, gs.p, reg.p, seen.p);
-        else {
-        HIP_OK(hipMemsetAsync(reg.p, 0, reg.bytes(), st));
-        HIP_OK(hipMemsetAsync(seen.p, 0, seen.bytes(), st));
-        const uint64_t m = sm.size();
-        DevBuf<uint64_t> ids(m + 1), front(m + 1);
-        if (m) {
-            h2d(ctx, ids.p, sm.data(), 8 * m);
-            hipLaunchKernelGGL(k_bfs_seed, dim3(s.grid(m)), dim3(kBlk), 0, st, (const uint64_t *)ids.p, m, id_lo, n,
-                               (const uint64_t *)gs.p, reg.p, seen.p, front.p);
-            LAUNCH_OK();
-        }
-        s.bfs(front, m, radius, true, gs.p, reg.p, seen.p);
-        }
+        region_bfs(std::vector<uint64_t>(a, b), radius, true);
+        const uint64_t fn = gather_region(fg);
+        reg.release();
+        seen.release();
+        gs.release();
+        return fn;
     }
-    mcaat_graph fg;
-    const uint64_t fn = s.gather_region(reg.p, &fg);
-    reg.release();
-    seen.release();
-    gs.release();
-    ctx->kstats["shard_fc_region_edges"].launches = fn;
-    if (verbose())
-        fprintf(stderr, "[mcaat] shard %d: %zu FindCycle starts, region %llu edges; %llu exchanges, %llu records\n",
-                comm.rank, starts.size(), (unsigned long long)fn, (unsigned long long)s.rt.rounds,
-                (unsigned long long)s.rt.records);
-    ctx->kstats["shard_exchanges"].launches = s.rt.rounds;
-    if (verbose())
-        fprintf(stderr, "[mcaat] shard %d: routing host ms: grouping %.1f, count all-gather %.1f, placement %.1f, "
-                        "all-to-all %.1f, replies %.1f\n",
-                comm.rank, s.rt.t_count, s.rt.t_gather, s.rt.t_place, s.rt.t_a2a, s.rt.t_reply);
-    mcaat_cycles local;
-    cf_find_cycles(&fg, p, s.to_compact(fg, fn, starts), &local, &comm);
-    {
+    void find_cycle() {
+        mcaat_graph fg;
+        const uint64_t fn = fc_region(&fg);
+        ctx->kstats["shard_fc_region_edges"].launches = fn;
+        if (verbose())
+            fprintf(stderr, "[mcaat] shard %d: %zu FindCycle starts, region %llu edges; %llu exchanges, %llu records\n",
+                    comm.rank, starts.size(), (unsigned long long)fn, (unsigned long long)rt.rounds,
+                    (unsigned long long)rt.records);
+        ctx->kstats["shard_exchanges"].launches = rt.rounds;
+        if (verbose())
+            fprintf(stderr, "[mcaat] shard %d: routing host ms: grouping %.1f, count all-gather %.1f, placement %.1f, "
+                            "all-to-all %.1f, replies %.1f\n",
+                    comm.rank, rt.t_count, rt.t_gather, rt.t_place, rt.t_a2a, rt.t_reply);
+        mcaat_cycles local;
+        cf_find_cycles(&fg, p, to_compact(fg, fn, starts), &local, &comm);
         // the results' compact ids back to edge ids in one translation: the starts, then every flat list
         std::vector<uint64_t> all(local.starts);
         for (const auto &fl : local.flat) all.insert(all.end(), fl.begin(), fl.end());
-        const std::vector<uint64_t> g_all = s.to_global(fg, fn, all);
+        const std::vector<uint64_t> g_all = to_global(fg, fn, all);
         size_t at = local.starts.size();
         for (size_t i = 0; i < local.starts.size(); ++i) {
             out->starts.push_back(g_all[i]);
@@ -2747,13 +2542,44 @@ void cycle_finder_sharded(mcaat_graph *g, const mcaat_cf_params &p, mcaat_cycles
             at += local.flat[i].size();
             out->offsets.push_back(std::move(local.offsets[i]));
         }
+        out->stats[5] = local.stats[5];
+        out->stats[6] = local.stats[6];
+        out->stats[7] = local.stats[7];
     }
-    out->stats[5] = local.stats[5];
-    out->stats[6] = local.stats[6];
-    out->stats[7] = local.stats[7];
-    timer.mark("find_cycle");
-    xr("find_cycle");
-    HIP_OK(hipStreamSynchronize(st));
+};
+}  // namespace
+
+void cycle_finder_sharded(mcaat_graph *g, const mcaat_cf_params &p, mcaat_cycles *out, Comm &comm) {
+    mcaat_ctx *ctx = g->ctx;
+    StageTimer timer(ctx);
+    if (!g->all_valid)
+        throw Error(MCAAT_E_INVALID, "per-shard CycleFinder needs the graph as built (every edge valid); unshard it first");
+    g->all_valid = false;
+    ShardCf s(g, comm, p, out);
+    // collectives per stage (kstats "xr_<stage>".launches): the bulk-synchronous rounds that bound
+    // this path at N ranks (DESIGN.md §7's model)
+    uint64_t xr_last = comm.n_coll, xq_last = comm.n_queued;
+    auto stage_done = [&](const char *stage) {
+        timer.mark(stage);
+        ctx->kstats[std::string("xr_") + stage].launches += comm.n_coll - xr_last;
+        ctx->kstats[std::string("xq_") + stage].launches += comm.n_queued - xq_last;  // of them queued
+        xr_last = comm.n_coll;
+        xq_last = comm.n_queued;
+    };
+    s.tips_filter();
+    stage_done("tips_filter");
+    s.peel();
+    stage_done("peel");
+    s.recount();
+    stage_done("recount");
+    s.dls_region();
+    stage_done("candidates");
+    s.dls_search();
+    s.fc_reach();
+    stage_done("dls");
+    s.find_cycle();
+    stage_done("find_cycle");
+    HIP_OK(hipStreamSynchronize(ctx->stream));
     timer.finish();
 }
 
@@ -2811,9 +2637,7 @@ void graph_unshard(mcaat_graph *g, Comm &comm) {
         DevBuf<uint64_t> dw0(N + 1), drl(N + 1);
         HIP_OK(hipMemcpyAsync(dw0.p, w0.data(), 8 * (N + 1), hipMemcpyHostToDevice, st));
         HIP_OK(hipMemcpyAsync(drl.p, g->rank_lo.data(), 8 * (N + 1), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_splice_bits, dim3(grid_for((D + 63) / 64, kBlk)), dim3(kBlk), 0, st, (const uint64_t *)locv.p,
-                           (const uint64_t *)dw0.p, (const uint64_t *)drl.p, N, D, g->valid.p);
-        LAUNCH_OK();
+        Launch(ctx, false).run((D + 63) / 64, k_splice_bits, locv.p, dw0.p, drl.p, N, D, g->valid.p);
         g->all_valid = false;
         HIP_OK(hipStreamSynchronize(st));
     }

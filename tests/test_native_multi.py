@@ -150,7 +150,16 @@ def _ranks(world, comm, extra=(), timeout=600):
                                          # tail from the first round on, checked every round
                                          (3, ("--knob", "dist.walk_block=0")),
                                          (3, ("--knob", "dist.walk_block=4194304", "--knob", "dist.walk_batch=1")),
-                                         (4, ("--knob", "dist.walk_block=4194304"))])
+                                         (4, ("--knob", "dist.walk_block=4194304")),
+                                         # every grid-stride launch of the sharded adjacency and the
+                                         # per-shard CycleFinder capped to one or two blocks (far more
+                                         # items than threads): the default forms, the message forms
+                                         # with the hop-by-hop BFS, the routed resolution and walk
+                                         (2, ("--knob", "dist.grid_blocks=2")), (3, ("--knob", "dist.grid_blocks=2")),
+                                         (2, ("--knob", "dist.grid_blocks=1", "--knob", "dist.adj_ranges=0",
+                                              "--knob", "dist.win_ranges=0", "--knob", "dist.bfs_sync=1")),
+                                         (3, ("--knob", "dist.grid_blocks=1", "--knob", "dist.res_fixed=0",
+                                              "--knob", "dist.walk_block=0"))])
 def test_sharded_build_and_cycle_finder_ranks_share_one_gpu(world, extra):
     """(round 5: per-shard CycleFinder by default) the sharded build + CycleFinder over 1-4 ranks
     sharing the GPU equal the one-GPU path: keys, multiplicities, valid bits after CycleFinder,
@@ -170,6 +179,21 @@ def test_per_shard_cycle_finder_parity_cases(case, world):
     shared-memory ranks (8: C4's partition, denser rulers above two ranks, eight target ranges)
     equals the one-GPU path: valid bitmap, candidates, buckets, entries, stats."""
     outs = _ranks(world, "shm", ("--case", case, "--slot", "0"))
+    for rc, o, e in outs:
+        assert rc == 0, (o[-2000:], e[-3000:])
+        assert "NATIVE_MULTI_OK" in o and "sharded=True" in o, o
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", ["pe_err", "low_thr", "c5_sample"])
+@pytest.mark.parametrize("world", [2, 3])
+def test_per_shard_cycle_finder_parity_cases_capped_grid(case, world):
+    """The parity cases with every grid-stride launch capped to two blocks (dist.grid_blocks=2,
+    512 threads), so each loop runs with more items than threads: the D-wide kernels in every
+    case (tens of thousands of edges per rank), and in c5_sample the region id translations over
+    the candidates too (26,663 candidates before DepthLevelSearch, counted at 2 ranks; pe_err and
+    low_thr have 92 and 118 after it, below one block). Same assertions as the uncapped cases."""
+    outs = _ranks(world, "shm", ("--case", case, "--slot", "0", "--knob", "dist.grid_blocks=2"))
     for rc, o, e in outs:
         assert rc == 0, (o[-2000:], e[-3000:])
         assert "NATIVE_MULTI_OK" in o and "sharded=True" in o, o
