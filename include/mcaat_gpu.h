@@ -288,6 +288,11 @@ int mcaat_comm_info(const mcaat_comm *c, int *world, int *rank);
  * rounds of any rank. No GPU, no communicator (this pool's boxes have one GPU, so the RCCL
  * transport's multi-rank grouping is exercised here on the host, not over xGMI). */
 int mcaat_comm_schedule_check(int world, uint64_t seed, uint64_t piece_bytes, uint64_t *rounds);
+/* Host-only: the strand-canonical form of one super-k-mer descriptor for edges of E symbols
+ * (csrc/desc_canon.h desc_canonical, the function node_counter's pass B runs on the device).
+ * in/out: {w0, w1}; w1 = bases [32,54) in bits 0..43 | n edges at 44 | hash bits at 50.
+ * MCAAT_E_INVALID unless 1 <= E <= 31 and n + E - 1 <= 54. No GPU. */
+int mcaat_desc_canonical(const uint64_t in[2], int E, uint64_t out[2]);
 int mcaat_comm_barrier(mcaat_comm *c);
 /* host memory: sizes[world] = every rank's byte count; then the bytes in rank order */
 int mcaat_comm_allgather_sizes(mcaat_comm *c, uint64_t bytes, uint64_t *sizes);

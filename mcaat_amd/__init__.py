@@ -16,6 +16,7 @@ from .lib import (  # noqa: F401
     Reads,
     SynthSpec,
     count_edges,
+    desc_canonical,
     edges_reduce,
     device_count,
     load_library,

@@ -11,6 +11,7 @@
 
 #include "internal.h"
 #include "comm.h"
+#include "desc_canon.h"
 #include "synth.h"
 
 using namespace mcaat;
@@ -1119,6 +1120,18 @@ int mcaat_comm_schedule_check(int world, uint64_t seed, uint64_t piece_bytes, ui
     return guarded([&] {
         const uint64_t r = comm_schedule_check(world, seed, piece_bytes);
         if (rounds) *rounds = r;
+    });
+}
+
+int mcaat_desc_canonical(const uint64_t in[2], int E, uint64_t out[2]) {
+    return guarded([&] {
+        require(in && out, "null argument");
+        require(E >= 1 && E <= kMaxK + 1, "E must be in [1, 31]");
+        require((int)((in[1] >> kNShift) & 63) + E - 1 <= kDescBases, "descriptor longer than its base field");
+        uint64_t w0 = in[0], w1 = in[1];
+        desc_canonical(w0, w1, E);
+        out[0] = w0;
+        out[1] = w1;
     });
 }
 

@@ -11,6 +11,9 @@
 //                     in LDS and scattered to 256 L1 buckets (top 8 hash bits).
 //   B  k_l2_hist / k_l2_scan / k_l2_scatter : one LDS-staged radix pass per L1 bucket
 //                     on the next l2_bits hash bits -> 2^(8+l2_bits) fine partitions.
+//                     k_l2_scatter also turns every descriptor's base string to its canonical
+//                     strand (desc_canon.h): pass A writes read orientation, and from pass B
+//                     on a locus read from either strand is one 128-bit value.
 //   C  k_lds_count  : one workgroup per fine partition; expands its super-k-mers and
 //                     counts canonical edges in an LDS open-addressing table; emits
 //                     (key, count). A partition whose distinct edges overflow the LDS
@@ -27,6 +30,7 @@
 #include <mutex>
 #include <type_traits>
 
+#include "desc_canon.h"
 #include "internal.h"
 
 namespace mcaat {
@@ -37,10 +41,7 @@ constexpr int kBlock = 256;
 
 // ---- super-k-mer descriptor (16 B) ----------------------------------------------------
 // w0: bases [0,32); w1: bases [32,54) in bits 0..43 | n edges (6 bits) at 44 | 14 hash bits at 50
-constexpr int kDescBases = 54;
-constexpr int kNShift = 44;
-constexpr int kHShift = 50;
-constexpr int kHBits = 14;
+// (kDescBases, kNShift, kHShift, kHBits and desc_canonical: desc_canon.h)
 
 struct SkParams {
     int E;        // edge length k+1
@@ -825,7 +826,7 @@ constexpr bool kCoopFlush = MCAAT_BCOOP != 0;  // completed lines written by the
 __global__ void __launch_bounds__(kBThreads) k_l2_scatter(const uint4 *__restrict__ data,
                                                           const uint16_t *__restrict__ sub,
                                                           const uint64_t *chunk_start, const uint32_t *chunk_len,
-                                                          const uint32_t *runs, int l2_bits,
+                                                          const uint32_t *runs, int l2_bits, int E,
                                                           uint4 *__restrict__ out, uint64_t gbase) {
     __shared__ uint4 buf[kMaxSub * kLG];
     __shared__ uint32_t lb[kMaxSub];  // this workgroup's run of each sub, in lines
@@ -856,7 +857,7 @@ __global__ void __launch_bounds__(kBThreads) k_l2_scatter(const uint4 *__restric
         const uint32_t i0 = i00 + j * kBThreads;
         if (i0 >= n) break;  // uniform: every thread reaches the same barriers
         const uint32_t cv = v[j];
-        const uint4 cd = d[j];
+        uint4 cd = d[j];
         const uint32_t ni = i0 + kBPF * kBThreads + threadIdx.x;
         v[j] = ni < n ? sub[s0 + ni] : kDeadSub;
         if (ni < n) d[j] = data[s0 + ni];
@@ -866,6 +867,11 @@ __global__ void __launch_bounds__(kBThreads) k_l2_scatter(const uint4 *__restric
         if (live) {
             r = atomicAdd(&lc[cv], 1u);
             line = bl[cv];
+            // strand-canonical from here on (pass C keys its collapse on all 128 bits); the
+            // arithmetic sits between the rank atomic's issue and the first use of its result
+            uint64_t w0 = (uint64_t)cd.x | ((uint64_t)cd.y << 32), w1 = (uint64_t)cd.z | ((uint64_t)cd.w << 32);
+            desc_canonical(w0, w1, E);
+            cd = make_uint4((uint32_t)w0, (uint32_t)(w0 >> 32), (uint32_t)w1, (uint32_t)(w1 >> 32));
             buffered = r / kLG == line;
             if (buffered) buf[cv * kLG + (r & (kLG - 1))] = cd;
             else out[(uint64_t)lb[cv] * kLG + r - gbase] = cd;
@@ -950,7 +956,6 @@ constexpr int kCB = MCAAT_CB;                              // descriptor loads i
 #define MCAAT_CPF 1
 #endif
 constexpr bool kCPF = MCAAT_CPF != 0;                      // next round's loads issued before the probes
-constexpr int kDefer = 64;                                 // descriptors with w0 == kEmpty before going raw
 #ifndef MCAAT_CPERCU
 #define MCAAT_CPERCU 2
 #endif
@@ -980,8 +985,6 @@ __device__ __forceinline__ void dma16(const uint4 *src, uint4 *lds) {
 __device__ __forceinline__ void wait_vm0() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 __device__ __forceinline__ void wait_vm1() { asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); }
 __device__ __forceinline__ void wait_lgkm0() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-// the deferred list only overflows on pathological T runs: those partitions go raw at once
-__device__ __forceinline__ bool n_deferred_over(uint32_t n) { return n > (uint32_t)kDefer; }
 
 // overflow-list entry: partition (24 bits), class (4), log2 class count (4)
 __device__ __forceinline__ uint32_t ovf_part(uint32_t e) { return e & 0xFFFFFFu; }
@@ -1050,10 +1053,7 @@ __global__ void __launch_bounds__(kCThreads, PERCU * kCThreads / 256) k_lds_coun
     uint32_t *const cnt = (uint32_t *)(keys + kCap);
     unsigned long long *const dk0 = (unsigned long long *)region, *const dk1 = dk0 + kDCap;
     uint32_t *const dcnt = (uint32_t *)(dk1 + kDCap);  // > 0: the slot holds a descriptor
-    // descriptors whose first word equals the empty marker (a run of >= 32 T) cannot be
-    // keyed in the descriptor table; they wait here and are expanded with weight 1
-    __shared__ uint4 deferred[kDefer];
-    __shared__ uint32_t n_deferred;
+    // (a strand-canonical descriptor's first word never equals the empty marker: desc_canon.h)
     __shared__ uint32_t n_distinct, n_ddistinct;
     __shared__ int ovf, dovf;
     __shared__ uint32_t todo[16];
@@ -1134,7 +1134,7 @@ __global__ void __launch_bounds__(kCThreads, PERCU * kCThreads / 256) k_lds_coun
             dcnt[i] = 0;
         }
         if (threadIdx.x == 0) {
-            n_distinct = n_ddistinct = n_deferred = 0;
+            n_distinct = n_ddistinct = 0;
             ovf = dovf = 0;
             ntodo = nt - 1;  // popped
         }
@@ -1145,18 +1145,10 @@ __global__ void __launch_bounds__(kCThreads, PERCU * kCThreads / 256) k_lds_coun
         // ---- 1: collapse identical descriptors ----
         // wait-free: the two key words are claimed separately, each by a CAS from empty; a
         // lane moves on as soon as either word holds another value, so no lane ever waits on
-        // another (a descriptor whose first word is the empty marker is deferred)
+        // another (pass B's canonical orientation keeps w0 off the empty marker)
         auto collapse = [&](uint64_t w0, uint64_t w1) {
             if (((w1 >> kNShift) & 63) == 0) return;  // padding
             if (((uint32_t)(w1 >> kHShift) & cmask) != cls) return;  // another class
-            if (w0 == kEmpty) {
-                const uint32_t j = atomicAdd(&n_deferred, 1u);
-                if (j < (uint32_t)kDefer)
-                    deferred[j] = make_uint4((uint32_t)w0, (uint32_t)(w0 >> 32), (uint32_t)w1, (uint32_t)(w1 >> 32));
-                else
-                    dovf = 1;
-                return;
-            }
             uint32_t h = desc_slot<kDCap>(w0, w1);
             for (int probe = 0; probe < kDProbe; ++probe, h = (h + 1) & (kDCap - 1)) {
                 unsigned long long k1 = dk1[h];
@@ -1243,7 +1235,7 @@ __global__ void __launch_bounds__(kCThreads, PERCU * kCThreads / 256) k_lds_coun
         }
         __syncthreads();
         tick(1);
-        if (dovf && lgn + (lgn == 0 ? split_first : 1u) <= split_max && !n_deferred_over(n_deferred)) {
+        if (dovf && lgn + (lgn == 0 ? split_first : 1u) <= split_max) {
             split();
             __syncthreads();  // every thread has read dovf and the stack before the next clear
             continue;
@@ -1251,7 +1243,9 @@ __global__ void __launch_bounds__(kCThreads, PERCU * kCThreads / 256) k_lds_coun
         if (PROF && threadIdx.x == 0) {
             if (dovf) tp[4]++;
             atomicAdd(&prof[6], (unsigned long long)n_ddistinct);
-            atomicAdd(&prof[7], (unsigned long long)(end - beg));
+            // "of" how many: the class's live descriptors, summed from the table below; a raw
+            // partition has no complete table and reports its rows (pass B's line padding included)
+            if (dovf) atomicAdd(&prof[7], (unsigned long long)(end - beg));
         }
 
         // ---- 2: expand into canonical edges ----
@@ -1308,23 +1302,23 @@ __global__ void __launch_bounds__(kCThreads, PERCU * kCThreads / 256) k_lds_coun
             cnt[i] = 0;
         }
         __syncthreads();
-        if (PROF && !raw) {  // expansion inserts: the distinct descriptors' edges
-            unsigned long long ins = 0;
+        if (PROF && !raw) {  // expansion inserts: the distinct descriptors' edges; their copies
+            unsigned long long ins = 0, live = 0;
 #pragma unroll
-            for (int j = 0; j < kSlots; ++j) ins += rc[j] ? (r1[j] >> kNShift) & 63 : 0;
-            for (int o = 32; o; o >>= 1) ins += __shfl_down(ins, o);
+            for (int j = 0; j < kSlots; ++j) {
+                ins += rc[j] ? (r1[j] >> kNShift) & 63 : 0;
+                live += rc[j];
+            }
+            for (int o = 32; o; o >>= 1) {
+                ins += __shfl_down(ins, o);
+                live += __shfl_down(live, o);
+            }
             if (lane == 0 && ins) atomicAdd(&prof[8], ins);
+            if (lane == 0 && live) atomicAdd(&prof[7], live);
         }
         if (!raw) {
 #pragma unroll
             for (int j = 0; j < kSlots; ++j) spread(r0[j], r1[j], (int)((r1[j] >> kNShift) & 63), rc[j]);
-            if (wave == 0) {
-                // n_deferred <= kDefer here (more sends the partition raw)
-                const bool live = (uint32_t)lane < n_deferred;
-                const uint4 q = live ? deferred[lane] : make_uint4(0, 0, 0, 0);
-                const uint64_t w0 = (uint64_t)q.x | ((uint64_t)q.y << 32), w1 = (uint64_t)q.z | ((uint64_t)q.w << 32);
-                spread(w0, w1, (int)((w1 >> kNShift) & 63), 1u);
-            }
         } else {
             for (uint64_t d0 = beg + (uint64_t)wave * 64; d0 < end; d0 += kCThreads) {
                 if (__hip_atomic_load(&ovf, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) break;
@@ -1987,7 +1981,7 @@ void node_counter_bc(mcaat_ctx *ctx, NcBuckets &bk, int k, CountResult &out) {
         auto *kt = new KernelTimer(ctx, "l2_partition", 34.0 * (double)gn, sb);  // sub rows + descriptors read, descriptors written
         if (c1 > c0) {
             hipLaunchKernelGGL(k_l2_scatter, dim3((unsigned)(c1 - c0)), dim3(kBThreads), 0, sb, l1.p, l1s.p,
-                               dcs.p + c0, dcl.p + c0, (const uint32_t *)druns.p + c0 * S, P.l2_bits, g.fine.p, gbase);
+                               dcs.p + c0, dcl.p + c0, (const uint32_t *)druns.p + c0 * S, P.l2_bits, E, g.fine.p, gbase);
             LAUNCH_OK();
         }
         kt->mark();

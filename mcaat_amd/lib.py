@@ -125,6 +125,7 @@ SIGNATURES = {
                                              _u8p]),
     "mcaat_comm_unique_id": (C.c_int, [_u8p]),
     "mcaat_comm_schedule_check": (C.c_int, [C.c_int, C.c_uint64, C.c_uint64, _u64p]),
+    "mcaat_desc_canonical": (C.c_int, [_u64p, C.c_int, _u64p]),
     "mcaat_comm_init_rccl": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _u8p, C.POINTER(C.c_void_p)]),
     "mcaat_comm_init_shm": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.c_uint64, C.POINTER(C.c_void_p)]),
     "mcaat_comm_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
@@ -176,6 +177,14 @@ def device_count() -> int:
     n = C.c_int(0)
     _check(load_library().mcaat_device_count(C.byref(n)))
     return n.value
+
+
+def desc_canonical(w0: int, w1: int, E: int) -> Tuple[int, int]:
+    """Strand-canonical form of a super-k-mer descriptor (mcaat_desc_canonical; host only)."""
+    src = (C.c_uint64 * 2)(w0, w1)
+    dst = (C.c_uint64 * 2)()
+    _check(load_library().mcaat_desc_canonical(src, int(E), dst))
+    return int(dst[0]), int(dst[1])
 
 
 def preload(device: int = 0) -> None:
