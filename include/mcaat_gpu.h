@@ -442,7 +442,22 @@ int mcaat_set_knob(mcaat_ctx *ctx, const char *name, int64_t value);
  *                      no effect), so that small inputs take every grid-stride loop with more items
  *                      than threads
  *   dist.segs_at_one  1: one rank runs the descriptor exchange through the segment all-to-all too
- *                      (its self-copy path; default 0 keeps the buckets in place) */
+ *                      (its self-copy path; default 0 keeps the buckets in place)
+ *   dist.preagg       1: every rank collapses its own descriptors before the descriptor exchange
+ *                      (pass B over its buckets, then identical descriptors of a fine partition become
+ *                      one record with a 32-bit multiplicity) and the owners count weighted
+ *                      descriptors; the graph is bit-identical. Only on the descriptor route
+ *                      (dist.desc = 1, dist.oriented = 0). Default 0: what it saves is link time.
+ *                      mcaat_kernel_timing's launch counts of "xb_desc" (bytes this rank handed to
+ *                      the exchange, either setting), "preagg_in" (live descriptors), "preagg_out"
+ *                      (records) and "preagg_raw" (records that left uncollapsed, weight 1) report it */
+
+/* The sender-side collapse of dist.preagg alone, on one rank's reads with no communicator: pass A,
+ * pass B and the collapse. out[0] = live descriptors in, out[1] = records out, out[2] = records
+ * emitted raw (a partition over the table's capacity past its deepest class split), out[3] = the
+ * sum of the emitted weights (= out[0]). Stage times: node_counter_a, shard_preagg.
+ * Replaces: nothing in the reference. */
+int mcaat_desc_preaggregate(mcaat_ctx *ctx, const mcaat_reads *r, int k, uint64_t out[4]);
 
 /* ---- allocator check ----------------------------------------------------------------------
  * Replaces: nothing in the reference. The device arena's stream order (csrc/alloc.hip): a block

@@ -17,6 +17,7 @@ from .lib import (  # noqa: F401
     SynthSpec,
     count_edges,
     desc_canonical,
+    desc_preaggregate,
     edges_reduce,
     device_count,
     load_library,

@@ -65,12 +65,21 @@ std::vector<uint64_t> choose_splits(const std::vector<uint64_t> &hist, int world
 // Replaces: the S2 counting of Read2SdbgS2::Run (sdbg_build.cpp:171-187) over reads split by rank.
 // Round 5: the buckets go out from where pass A wrote them (one segment per bucket, grouped per
 // owner: Comm::alltoallv_dev_segs), with no full-size send buffer; one rank keeps its buckets.
-static void exchange_descriptors(mcaat_ctx *ctx, Comm &comm, NcBuckets &bk, NcBuckets &own, uint64_t occ_total) {
+// (dist.preagg) After a sender-side collapse (node_counter_preagg) the buckets hold (descriptor,
+// weight) records: the weights go out as a third segment set, the owner ranges are cut by record
+// counts, and the owner's share of the edge occurrences still follows the slots before the
+// collapse (pre_slots), so its count output is sized as without the collapse.
+// xb: the bytes this rank hands to the exchange, its own share included.
+static void exchange_descriptors(mcaat_ctx *ctx, Comm &comm, NcBuckets &bk, NcBuckets &own, uint64_t occ_total,
+                                 uint64_t *xb) {
     const int N = comm.world, R = comm.rank;
-    std::vector<uint64_t> mine(256, 0);
+    const bool weighted = bk.wgt.p != nullptr;
+    std::vector<uint64_t> mine(512, 0);  // per bucket: slots to send; slots before the collapse
     for (int b = 0; b < 256; ++b) {
         if (bk.regions[b].size() > 1) throw Error(MCAAT_E_INVALID, "descriptor exchange: one region per bucket expected");
         for (const auto &rg : bk.regions[b]) mine[b] += rg.second;
+        mine[256 + b] = weighted ? bk.pre_slots[b] : mine[b];
+        *xb += (weighted ? 22 : 18) * mine[b];
     }
     // dist.segs_at_one=1 (tests): one rank runs the exchange too (its segments are the
     // transport's self-copies), so the segment all-to-all is exercised on a one-GPU box
@@ -79,11 +88,11 @@ static void exchange_descriptors(mcaat_ctx *ctx, Comm &comm, NcBuckets &bk, NcBu
         own.n_occ = occ_total;
         return;
     }
-    const std::vector<uint64_t> all = comm.allgather_vec(mine);  // [rank][bucket]
+    const std::vector<uint64_t> all = comm.allgather_vec(mine);  // [rank][bucket, 256 + bucket]
     std::vector<double> cum(256);
     double acc = 0;
     for (int b = 0; b < 256; ++b) {
-        for (int q = 0; q < N; ++q) acc += (double)all[(uint64_t)q * 256 + b];
+        for (int q = 0; q < N; ++q) acc += (double)all[(uint64_t)q * 512 + b];
         cum[b] = acc;
     }
     // owner o takes buckets [lo[o], lo[o+1])
@@ -94,36 +103,46 @@ static void exchange_descriptors(mcaat_ctx *ctx, Comm &comm, NcBuckets &bk, NcBu
         lo[o] = std::min(std::max(b, lo[o - 1]), 256);
     }
     // to owner q: one segment per non-empty bucket of its range, descriptors and sub rows
-    std::vector<std::vector<Comm::Seg>> s16(N), s2(N);
+    std::vector<std::vector<Comm::Seg>> s16(N), s2(N), s4(N);
     for (int q = 0; q < N; ++q)
         for (int b = lo[q]; b < lo[q + 1]; ++b)
             for (const auto &rg : bk.regions[b]) {
                 s16[q].push_back({bk.data.p + rg.first, 16 * rg.second});
                 s2[q].push_back({bk.sub.p + rg.first, 2 * rg.second});
+                if (weighted) s4[q].push_back({bk.wgt.p + rg.first, 4 * rg.second});
             }
     // from source q: its non-empty buckets of [lo[R], lo[R+1]), in bucket order
-    std::vector<std::vector<uint64_t>> r16(N), r2(N);
+    std::vector<std::vector<uint64_t>> r16(N), r2(N), r4(N);
     uint64_t n_recv = 0;
+    double pre_all = 0, pre_own = 0;  // slots before the collapse: every bucket's, this owner's
     own.regions.assign(256, {});
-    for (int q = 0; q < N; ++q)
+    for (int q = 0; q < N; ++q) {
+        for (int b = 0; b < 256; ++b) pre_all += (double)all[(uint64_t)q * 512 + 256 + b];
         for (int b = lo[R]; b < lo[R + 1]; ++b) {
-            const uint64_t n = all[(uint64_t)q * 256 + b];
+            const uint64_t n = all[(uint64_t)q * 512 + b];
+            pre_own += (double)all[(uint64_t)q * 512 + 256 + b];
             if (!n) continue;
             r16[q].push_back(16 * n);
             r2[q].push_back(2 * n);
+            r4[q].push_back(4 * n);
             own.regions[b].push_back({n_recv, n});
             n_recv += n;
         }
+    }
     own.data.alloc(n_recv ? n_recv : 1);
     own.sub.alloc(n_recv ? n_recv : 8);
+    if (weighted) own.wgt.alloc(n_recv ? n_recv : 8);
     HIP_OK(hipStreamSynchronize(ctx->stream));
     comm.alltoallv_dev_segs(s16, own.data.p, r16);
     comm.alltoallv_dev_segs(s2, own.sub.p, r2);
+    if (weighted) comm.alltoallv_dev_segs(s4, own.wgt.p, r4);
     bk.data.release();
     bk.sub.release();
+    bk.wgt.release();
     own.l2_bits = bk.l2_bits;
-    // occurrences behind this owner's descriptors (sizes its output buffer), by its share
-    own.n_occ = acc > 0 ? (uint64_t)((double)occ_total * (double)n_recv / acc) + 1 : 0;
+    // occurrences behind this owner's descriptors (sizes its output buffer), by its share of the
+    // slots pass A wrote (the same figure with and without a sender-side collapse)
+    own.n_occ = pre_all > 0 ? (uint64_t)((double)occ_total * pre_own / pre_all) + 1 : 0;
 }
 
 void build_graph_sharded(mcaat_ctx *ctx, Comm &comm, const mcaat_reads *r, int k, mcaat_graph *g) {
@@ -143,7 +162,21 @@ void build_graph_sharded(mcaat_ctx *ctx, Comm &comm, const mcaat_reads *r, int k
                        },
                        bk);
         timer.mark("node_counter_a");
-        exchange_descriptors(ctx, comm, bk, own, occ_total);
+        // dist.preagg=1: identical descriptors collapse on the sender first and travel once, with
+        // a multiplicity (off by default: its gain is link time, which a one-GPU box cannot show)
+        if (knob(ctx, "dist.preagg", 0) != 0) {
+            NcBuckets agg;
+            uint64_t ps[4];
+            node_counter_preagg(ctx, bk, k, agg, ps);
+            bk = std::move(agg);
+            ctx->kstats["preagg_in"].launches += ps[0];
+            ctx->kstats["preagg_out"].launches += ps[1];
+            ctx->kstats["preagg_raw"].launches += ps[2];
+            timer.mark("shard_preagg");
+        }
+        uint64_t xb = 0;
+        exchange_descriptors(ctx, comm, bk, own, occ_total, &xb);
+        ctx->kstats["xb_desc"].launches += xb;
         timer.mark("shard_desc_all_to_all");
         node_counter_bc(ctx, own, k, c);
         timer.mark("node_counter_bc");

@@ -426,14 +426,26 @@ struct NcBuckets {
     DevBuf<uint4> data;     // 16-B super-k-mer descriptors
     DevBuf<uint16_t> sub;   // each one's fine sub-partition row (same slots)
     // per L1 bucket: its regions (first slot, slots) in data/sub, each a whole number of
-    // kMini-slot reservations (256 slots: every region starts 16-B aligned in sub)
+    // kMini-slot reservations (256 slots: every region starts 16-B aligned in sub), or, after a
+    // sender-side collapse, of 8-slot groups
     std::vector<std::vector<std::pair<uint64_t, uint64_t>>> regions;
     // pass A's layout: bucket b's slots start at base[b] (257 entries; a bucket's reserved but
     // unused tail is not part of its region). Empty when the regions came from an exchange.
     std::vector<uint64_t> base;
     int l2_bits = 0;        // fine partitions = 256 << l2_bits
     uint64_t n_occ = 0;     // edge occurrences behind the descriptors (sizes the output)
+    // (dist.preagg) each slot's multiplicity, when the slots are (descriptor, weight) records of a
+    // sender-side collapse; empty on every other path. pre_slots: the slots per L1 bucket before
+    // the collapse (256 entries; the exchange's share rule for n_occ)
+    DevBuf<uint32_t> wgt;
+    std::vector<uint64_t> pre_slots;
 };
+// the sender-side collapse of a sharded build (dist.preagg): pass B over this rank's own buckets,
+// then identical descriptors of a fine partition become one (descriptor, weight) record in a
+// region per L1 bucket of `out` (whole 8-slot groups, sub rows written). stats: live descriptors
+// in, records out, records emitted raw (weight 1, table overflow), sum of the emitted weights.
+// Releases in's buffers.
+void node_counter_preagg(mcaat_ctx *ctx, NcBuckets &in, int k, NcBuckets &out, uint64_t stats[4]);
 int nc_fine_bits(mcaat_ctx *ctx, uint64_t n_occ);
 void node_counter_a(mcaat_ctx *ctx, const mcaat_reads *r, int k, const std::function<int(uint64_t)> &pick, NcBuckets &b);
 void node_counter_bc(mcaat_ctx *ctx, NcBuckets &b, int k, CountResult &out);

@@ -18,6 +18,9 @@
 //                     counts canonical edges in an LDS open-addressing table; emits
 //                     (key, count). A partition whose distinct edges overflow the LDS
 //                     table is re-counted by the global-table fallback (k_fallback).
+//   (a sharded build with dist.preagg: k_desc_preagg collapses a rank's own descriptors after
+//   its pass B into (descriptor, weight) records for the exchange, and the owner's B and C run
+//   their WEIGHTED instantiations over them)
 // Output order is irrelevant: sdbg_build sorts by BOSS key.
 #include <hipcub/hipcub.hpp>
 
@@ -823,11 +826,17 @@ constexpr int kBPF = MCAAT_BPF;  // rounds of descriptor loads in flight
 #endif
 constexpr bool kCoopFlush = MCAAT_BCOOP != 0;  // completed lines written by the whole wave
 
+// WEIGHTED (a sharded build's owner after a sender-side collapse, dist.preagg): each descriptor's
+// 32-bit multiplicity goes to the same fine-partition slot of out_w, written directly (the line
+// buffers stay descriptors only: 128 KB of the 160); line padding gets weight 0.
+template <bool WEIGHTED>
 __global__ void __launch_bounds__(kBThreads) k_l2_scatter(const uint4 *__restrict__ data,
                                                           const uint16_t *__restrict__ sub,
                                                           const uint64_t *chunk_start, const uint32_t *chunk_len,
                                                           const uint32_t *runs, int l2_bits, int E,
-                                                          uint4 *__restrict__ out, uint64_t gbase) {
+                                                          uint4 *__restrict__ out, uint64_t gbase,
+                                                          const uint32_t *__restrict__ wgt,
+                                                          uint32_t *__restrict__ out_w) {
     __shared__ uint4 buf[kMaxSub * kLG];
     __shared__ uint32_t lb[kMaxSub];  // this workgroup's run of each sub, in lines
     __shared__ uint32_t lc[kMaxSub];  // descriptors per sub placed so far
@@ -867,6 +876,7 @@ __global__ void __launch_bounds__(kBThreads) k_l2_scatter(const uint4 *__restric
         if (live) {
             r = atomicAdd(&lc[cv], 1u);
             line = bl[cv];
+            if constexpr (WEIGHTED) out_w[(uint64_t)lb[cv] * kLG + r - gbase] = wgt[s0 + i0 + threadIdx.x];
             // strand-canonical from here on (pass C keys its collapse on all 128 bits); the
             // arithmetic sits between the rank atomic's issue and the first use of its result
             uint64_t w0 = (uint64_t)cd.x | ((uint64_t)cd.y << 32), w1 = (uint64_t)cd.z | ((uint64_t)cd.w << 32);
@@ -927,6 +937,8 @@ __global__ void __launch_bounds__(kBThreads) k_l2_scatter(const uint4 *__restric
             uint4 *o = out + (((uint64_t)lb[i] + k / kLG) * kLG - gbase);
 #pragma unroll
             for (uint32_t z = 0; z < kLG; ++z) o[z] = z < (k & (kLG - 1)) ? buf[i * kLG + z] : make_uint4(0, 0, 0, 0);
+            if constexpr (WEIGHTED)
+                for (uint32_t z = k & (kLG - 1); z < kLG; ++z) out_w[((uint64_t)lb[i] + k / kLG) * kLG - gbase + z] = 0;
         }
     }
 }
@@ -1028,7 +1040,10 @@ __device__ __forceinline__ uint32_t desc_slot(uint64_t w0, uint64_t w1) {
     return (uint32_t)(x >> (64 - (DCAP == 4096 ? 12 : 11)));
 }
 
-template <bool PROF, int kCap, int PERCU>
+// WEIGHTED (dist.preagg: the owner's input is (descriptor, multiplicity) records): wgt holds each
+// slot's multiplicity beside data; the collapse adds it instead of 1, the raw expansion adds it
+// per edge.
+template <bool PROF, int kCap, int PERCU, bool WEIGHTED>
 __global__ void __launch_bounds__(kCThreads, PERCU * kCThreads / 256) k_lds_count(const uint4 *__restrict__ data, uint64_t gbase,
                                                          const uint64_t *__restrict__ fine_base, uint64_t p0,
                                                          uint64_t F, int E,
@@ -1036,7 +1051,8 @@ __global__ void __launch_bounds__(kCThreads, PERCU * kCThreads / 256) k_lds_coun
                                                          unsigned long long *out_cursor, uint32_t *ovf_list,
                                                          unsigned long long *ovf_n, uint32_t cap_max, uint32_t dmax,
                                                          unsigned long long *split_n, uint32_t split_first,
-                                                         uint32_t split_max, unsigned long long *prof) {
+                                                         uint32_t split_max, unsigned long long *prof,
+                                                         const uint32_t *__restrict__ wgt) {
     static_assert(cap_lg(kCap) >= 0, "edge table of 4096, 6144 or 8192 slots");
     constexpr int kDCap = dcap_for(kCap);  // descriptor slots of this tier
     // The descriptor table (phase 1) and the edge table (phases 2-3) share one LDS region:
@@ -1146,7 +1162,7 @@ __global__ void __launch_bounds__(kCThreads, PERCU * kCThreads / 256) k_lds_coun
         // wait-free: the two key words are claimed separately, each by a CAS from empty; a
         // lane moves on as soon as either word holds another value, so no lane ever waits on
         // another (pass B's canonical orientation keeps w0 off the empty marker)
-        auto collapse = [&](uint64_t w0, uint64_t w1) {
+        auto collapse = [&](uint64_t w0, uint64_t w1, uint32_t wt) {  // wt: 1 unless WEIGHTED
             if (((w1 >> kNShift) & 63) == 0) return;  // padding
             if (((uint32_t)(w1 >> kHShift) & cmask) != cls) return;  // another class
             uint32_t h = desc_slot<kDCap>(w0, w1);
@@ -1166,7 +1182,7 @@ __global__ void __launch_bounds__(kCThreads, PERCU * kCThreads / 256) k_lds_coun
                     if (k0 == kEmpty) k0 = w0;
                 }
                 if (k0 != w0) continue;
-                atomicAdd(&dcnt[h], 1u);
+                atomicAdd(&dcnt[h], wt);
                 return;
             }
             dovf = 1;
@@ -1197,8 +1213,11 @@ __global__ void __launch_bounds__(kCThreads, PERCU * kCThreads / 256) k_lds_coun
                     wait_lgkm0();  // the read has landed before the DMA may overwrite the slot
                     issue(d0 + (uint64_t)kCRing * kCThreads, slot);
                 }
-                if (d < end)
-                    collapse((uint64_t)cq.x | ((uint64_t)cq.y << 32), (uint64_t)cq.z | ((uint64_t)cq.w << 32));
+                if (d < end) {
+                    uint32_t wt = 1u;
+                    if constexpr (WEIGHTED) wt = wgt[d];
+                    collapse((uint64_t)cq.x | ((uint64_t)cq.y << 32), (uint64_t)cq.z | ((uint64_t)cq.w << 32), wt);
+                }
                 slot = slot + 1 == kCRing ? 0 : slot + 1;
             }
             wait_vm0();  // no DMA may land in the region once it becomes the edge table
@@ -1206,31 +1225,39 @@ __global__ void __launch_bounds__(kCThreads, PERCU * kCThreads / 256) k_lds_coun
         // kCB descriptors per thread per round: their loads are all in flight together, and
         // with kCPF the next round's are issued before this round's probes
         uint4 q[kCB];
+        uint32_t qw[kCB];  // WEIGHTED: the slots' multiplicities, loaded beside the descriptors
         if (kCPF) {
 #pragma unroll
             for (int k = 0; k < kCB; ++k) {
                 const uint64_t d = beg + threadIdx.x + (uint64_t)k * kCThreads;
                 q[k] = d < end ? data[d] : make_uint4(0, 0, 0, 0);
+                if constexpr (WEIGHTED) qw[k] = d < end ? wgt[d] : 0u;
             }
         }
         for (uint64_t d0 = beg + threadIdx.x; d0 < end; d0 += (uint64_t)kCThreads * kCB) {
             if (__hip_atomic_load(&dovf, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) break;
             uint4 cq[kCB];
+            uint32_t cw[kCB];
 #pragma unroll
             for (int k = 0; k < kCB; ++k) {
+                cw[k] = 1u;
                 if (kCPF) {
                     cq[k] = q[k];
+                    if constexpr (WEIGHTED) cw[k] = qw[k];
                     const uint64_t d = d0 + (uint64_t)(k + kCB) * kCThreads;
                     q[k] = d < end ? data[d] : make_uint4(0, 0, 0, 0);
+                    if constexpr (WEIGHTED) qw[k] = d < end ? wgt[d] : 0u;
                 } else {
                     const uint64_t d = d0 + (uint64_t)k * kCThreads;
                     cq[k] = d < end ? data[d] : make_uint4(0, 0, 0, 0);
+                    if constexpr (WEIGHTED) cw[k] = d < end ? wgt[d] : 0u;
                 }
             }
 #pragma unroll
             for (int k = 0; k < kCB; ++k)
                 if (d0 + (uint64_t)k * kCThreads < end)
-                    collapse((uint64_t)cq[k].x | ((uint64_t)cq[k].y << 32), (uint64_t)cq[k].z | ((uint64_t)cq[k].w << 32));
+                    collapse((uint64_t)cq[k].x | ((uint64_t)cq[k].y << 32), (uint64_t)cq[k].z | ((uint64_t)cq[k].w << 32),
+                             cw[k]);
         }
         }
         __syncthreads();
@@ -1324,13 +1351,15 @@ __global__ void __launch_bounds__(kCThreads, PERCU * kCThreads / 256) k_lds_coun
                 if (__hip_atomic_load(&ovf, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) break;
                 const uint64_t d = d0 + lane;
                 uint64_t w0 = 0, w1 = 0;
+                uint32_t wt = 1u;
                 if (d < end) {
                     const uint4 q = data[d];
                     w0 = (uint64_t)q.x | ((uint64_t)q.y << 32);
                     w1 = (uint64_t)q.z | ((uint64_t)q.w << 32);
+                    if constexpr (WEIGHTED) wt = wgt[d];
                     if (((uint32_t)(w1 >> kHShift) & cmask) != cls) w0 = w1 = 0;
                 }
-                spread(w0, w1, (int)((w1 >> kNShift) & 63), 1u);
+                spread(w0, w1, (int)((w1 >> kNShift) & 63), wt);
             }
         }
         __syncthreads();
@@ -1399,7 +1428,7 @@ struct __attribute__((aligned(16))) Slot {
 };
 
 __device__ __forceinline__ void table_insert(uint64_t key, Slot *tab, uint64_t mask, unsigned long long *n_new,
-                                             int *overflow) {
+                                             int *overflow, uint32_t weight) {
     const unsigned long long k1 = key + 1;
     uint64_t slot = mix64(key) & mask;
     for (uint32_t probe = 0; probe < kMaxProbe; ++probe) {
@@ -1407,13 +1436,13 @@ __device__ __forceinline__ void table_insert(uint64_t key, Slot *tab, uint64_t m
         if (cur == 0) {
             cur = atomicCAS(&tab[slot].key1, 0ull, k1);
             if (cur == 0) {
-                atomicAdd(&tab[slot].cnt, 1u);
+                atomicAdd(&tab[slot].cnt, weight);
                 atomicAdd(n_new, 1ull);
                 return;
             }
         }
         if (cur == k1) {
-            atomicAdd(&tab[slot].cnt, 1u);
+            atomicAdd(&tab[slot].cnt, weight);
             return;
         }
         slot = (slot + 1) & mask;
@@ -1421,15 +1450,23 @@ __device__ __forceinline__ void table_insert(uint64_t key, Slot *tab, uint64_t m
     atomicExch(overflow, 1);
 }
 
+// WEIGHTED (here and in k_fallback): wgt holds each slot's multiplicity; an edge occurs, and is
+// added, that many times per record
+template <bool WEIGHTED>
 __global__ void __launch_bounds__(kBlock) k_part_occ(const uint4 *data, uint64_t gbase, const uint64_t *fine_base,
-                                                     const uint32_t *parts, uint64_t np, uint64_t *occ) {
+                                                     const uint32_t *parts, uint64_t np, uint64_t *occ,
+                                                     const uint32_t *wgt) {
     for (uint64_t q = blockIdx.x; q < np; q += gridDim.x) {
         const uint32_t e = parts[q];
         const uint64_t p = ovf_part(e);
         unsigned long long acc = 0;
         for (uint64_t d = fine_base[p] - gbase + threadIdx.x; d < fine_base[p + 1] - gbase; d += blockDim.x) {
             const uint32_t dw = data[d].w;
-            if (ovf_in_class(e, dw)) acc += (dw >> (kNShift - 32)) & 63;
+            if constexpr (WEIGHTED) {
+                if (ovf_in_class(e, dw)) acc += (unsigned long long)((dw >> (kNShift - 32)) & 63) * wgt[d];
+            } else {
+                if (ovf_in_class(e, dw)) acc += (dw >> (kNShift - 32)) & 63;
+            }
         }
         __shared__ unsigned long long s;
         if (threadIdx.x == 0) s = 0;
@@ -1441,9 +1478,11 @@ __global__ void __launch_bounds__(kBlock) k_part_occ(const uint4 *data, uint64_t
     }
 }
 
+template <bool WEIGHTED>
 __global__ void __launch_bounds__(kBlock) k_fallback(const uint4 *data, uint64_t gbase, const uint64_t *fine_base,
                                                      const uint32_t *parts, uint64_t np, int E, Slot *tab,
-                                                     uint64_t mask, unsigned long long *n_new, int *overflow) {
+                                                     uint64_t mask, unsigned long long *n_new, int *overflow,
+                                                     const uint32_t *wgt) {
     for (uint64_t q = blockIdx.x; q < np; q += gridDim.x) {
         const uint32_t e = parts[q];
         const uint64_t p = ovf_part(e);
@@ -1453,7 +1492,10 @@ __global__ void __launch_bounds__(kBlock) k_fallback(const uint4 *data, uint64_t
             const uint64_t w0 = (uint64_t)x.x | ((uint64_t)x.y << 32);
             const uint64_t w1 = (uint64_t)x.z | ((uint64_t)x.w << 32);
             const int n = (int)((w1 >> kNShift) & 63);
-            for (int i = 0; i < n; ++i) table_insert(canon_edge(desc_window(w0, w1, i, E), E), tab, mask, n_new, overflow);
+            uint32_t wt = 1u;
+            if constexpr (WEIGHTED) wt = wgt[d];
+            for (int i = 0; i < n; ++i)
+                table_insert(canon_edge(desc_window(w0, w1, i, E), E), tab, mask, n_new, overflow, wt);
         }
     }
 }
@@ -1477,6 +1519,211 @@ __global__ void __launch_bounds__(kBlock) k_fallback_emit(const Slot *tab, uint6
                 out_cnt[o] = tab[i].cnt;
             }
         }
+    }
+}
+
+// ---- sender-side collapse of a sharded build (dist.preagg) -----------------------------------
+// Before the descriptor exchange a rank runs pass B over its own buckets and then collapses each
+// fine partition's identical descriptors in LDS (pass C's wait-free table: two key words, each
+// claimed by a CAS from empty, and a 32-bit count), so every distinct descriptor goes to its
+// owner once, with its multiplicity. One workgroup per fine partition; 40 KB of LDS, two
+// workgroups per CU as in pass C. A partition whose distinct descriptors exceed the table is
+// split into classes on the spare hash bits like pass C's; past the deepest split the class
+// leaves raw, one record of weight 1 per descriptor (the owner collapses again, so a raw record
+// is only a missed saving).
+constexpr int kPThreads = 1024;
+constexpr int kPWaves = kPThreads / 64;
+constexpr int kPSlots = kDCap / kPThreads;  // table slots per thread
+static_assert(kDCap % kPThreads == 0, "whole descriptor slots per thread");
+
+// live (n > 0) descriptors per L1 bucket, from the sub rows: the capacities of the collapse's
+// output regions
+__global__ void __launch_bounds__(kBlock) k_live_count(const uint16_t *__restrict__ sub, const uint64_t *chunk_start,
+                                                       const uint32_t *chunk_len, const uint32_t *chunk_bucket,
+                                                       uint64_t nch, unsigned long long *live) {
+    for (uint64_t c = blockIdx.x; c < nch; c += gridDim.x) {
+        const uint64_t s0 = chunk_start[c];
+        const uint32_t n = chunk_len[c];
+        unsigned long long acc = 0;
+        for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) acc += sub[s0 + i] != kDeadSub;
+        block_add(&live[chunk_bucket[c]], acc);
+    }
+}
+
+// stat: [0] records emitted raw, [1] sum of the emitted weights
+__global__ void __launch_bounds__(kPThreads, 2 * kPThreads / 256)
+k_desc_preagg(const uint4 *__restrict__ data, uint64_t gbase, const uint64_t *__restrict__ fine_base, uint64_t p0,
+              uint64_t F, int l2_bits, uint4 *__restrict__ out, uint16_t *__restrict__ out_sub,
+              uint32_t *__restrict__ out_w, const uint64_t *__restrict__ rbase, const uint64_t *__restrict__ rcap,
+              unsigned long long *rcur, uint32_t dmax, uint32_t split_first, uint32_t split_max,
+              unsigned long long *stat) {
+    __shared__ unsigned long long dk0[kDCap], dk1[kDCap];
+    __shared__ uint32_t dcnt[kDCap];  // > 0: the slot holds a descriptor
+    __shared__ uint32_t n_ddistinct;
+    __shared__ int dovf;
+    __shared__ uint32_t todo[16];
+    __shared__ int ntodo;
+    __shared__ uint32_t wsum[kPWaves];
+    __shared__ unsigned long long obase;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long below = (1ull << lane) - 1;  // lanes before this one
+    unsigned long long wacc = 0;                           // weights this thread emitted
+    for (uint64_t p = p0 + blockIdx.x; p < F; p += gridDim.x) {
+        const uint64_t beg = fine_base[p] - gbase, end = fine_base[p + 1] - gbase;
+        if (beg == end) continue;  // uniform
+        const uint32_t b = (uint32_t)(p >> l2_bits);
+        const uint64_t ob = rbase[b], ocap = rcap[b];
+        if (threadIdx.x == 0) {
+            todo[0] = 0;
+            ntodo = 1;
+        }
+        __syncthreads();
+        // the classes still to do, a stack of (cls | lgn << 4), as in k_lds_count
+        for (;;) {
+            const int nt = ntodo;
+            const uint32_t item = nt ? todo[nt - 1] : 0u;
+            __syncthreads();  // every thread has read the top before thread 0 pops it
+            if (nt == 0) break;
+            const uint32_t cls = item & 15, lgn = item >> 4;
+            const uint32_t cmask = (1u << lgn) - 1;
+            for (int i = threadIdx.x; i < kDCap; i += kPThreads) {
+                dk0[i] = dk1[i] = kEmpty;
+                dcnt[i] = 0;
+            }
+            if (threadIdx.x == 0) {
+                n_ddistinct = 0;
+                dovf = 0;
+                ntodo = nt - 1;  // popped
+            }
+            __syncthreads();
+            // live descriptors of this class (padding has n = 0)
+            auto mine = [&](const uint4 &q) {
+                return ((q.w >> (kNShift - 32)) & 63) != 0 && ((q.w >> (kHShift - 32)) & cmask) == cls;
+            };
+            auto collapse = [&](uint64_t w0, uint64_t w1) {
+                uint32_t h = desc_slot<kDCap>(w0, w1);
+                for (int probe = 0; probe < kDProbe; ++probe, h = (h + 1) & (kDCap - 1)) {
+                    unsigned long long k1 = dk1[h];
+                    if (k1 == kEmpty) {
+                        k1 = atomicCAS(&dk1[h], kEmpty, (unsigned long long)w1);
+                        if (k1 == kEmpty) {
+                            k1 = w1;
+                            if (atomicAdd(&n_ddistinct, 1u) + 1 > dmax) dovf = 1;
+                        }
+                    }
+                    if (k1 != w1) continue;
+                    unsigned long long k0 = dk0[h];
+                    if (k0 == kEmpty) {
+                        k0 = atomicCAS(&dk0[h], kEmpty, (unsigned long long)w0);
+                        if (k0 == kEmpty) k0 = w0;
+                    }
+                    if (k0 != w0) continue;
+                    atomicAdd(&dcnt[h], 1u);
+                    return;
+                }
+                dovf = 1;
+            };
+            // one descriptor per thread per round, the next round's load in flight
+            uint4 q = beg + threadIdx.x < end ? data[beg + threadIdx.x] : make_uint4(0, 0, 0, 0);
+            for (uint64_t d = beg + threadIdx.x; d < end; d += kPThreads) {
+                if (__hip_atomic_load(&dovf, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) break;
+                const uint4 cq = q;
+                const uint64_t dn = d + kPThreads;
+                if (dn < end) q = data[dn];
+                if (mine(cq)) collapse((uint64_t)cq.x | ((uint64_t)cq.y << 32), (uint64_t)cq.z | ((uint64_t)cq.w << 32));
+            }
+            __syncthreads();
+            const bool raw = dovf != 0;
+            if (raw && lgn + (lgn == 0 ? split_first : 1u) <= split_max) {
+                if (threadIdx.x == 0) {
+                    const uint32_t sb = lgn == 0 ? split_first : 1u;
+                    for (uint32_t j = (1u << sb); j-- > 0;) todo[ntodo++] = (cls + (j << lgn)) | ((lgn + sb) << 4);
+                }
+                __syncthreads();  // every thread has read dovf and the stack before the next clear
+                continue;
+            }
+            // records of this class per wave: the occupied table slots, or (raw) its descriptors
+            uint32_t c[kPSlots];
+            unsigned long long m[kPSlots];
+            uint32_t wtotal = 0;
+            if (!raw) {
+#pragma unroll
+                for (int j = 0; j < kPSlots; ++j) {
+                    c[j] = dcnt[threadIdx.x + j * kPThreads];
+                    m[j] = __ballot(c[j] != 0);
+                    wtotal += (uint32_t)__popcll(m[j]);
+                }
+            } else {
+                for (uint64_t d0 = beg + (uint64_t)wave * 64; d0 < end; d0 += kPThreads) {
+                    const uint64_t d = d0 + lane;
+                    wtotal += (uint32_t)__popcll(__ballot(d < end && mine(data[d])));
+                }
+            }
+            if (lane == 0) wsum[wave] = wtotal;
+            __syncthreads();
+            if (threadIdx.x == 0) {  // one cursor atomic per workgroup and class
+                uint32_t t = 0;
+                for (int w = 0; w < kPWaves; ++w) {
+                    const uint32_t v = wsum[w];
+                    wsum[w] = t;
+                    t += v;
+                }
+                obase = t ? atomicAdd(&rcur[b], (unsigned long long)t) : 0;
+                if (raw && t) atomicAdd(&stat[0], (unsigned long long)t);
+            }
+            __syncthreads();
+            // a record past the region's capacity is dropped: the cursor keeps counting and the
+            // host reports it (the capacity is the bucket's live descriptors, so none is)
+            const int sub_shift = 64 - l2_bits;
+            auto put = [&](uint64_t o, const uint4 &dsc, uint32_t wt) {
+                if (o < ocap) {
+                    out[ob + o] = dsc;
+                    out_w[ob + o] = wt;
+                    const uint64_t hi = (uint64_t)dsc.w << 32;
+                    out_sub[ob + o] = (uint16_t)(sub_shift < 64 ? hi >> sub_shift : 0);
+                    wacc += wt;
+                }
+            };
+            uint64_t o = obase + wsum[wave];
+            if (!raw) {
+#pragma unroll
+                for (int j = 0; j < kPSlots; ++j) {
+                    if (c[j]) {
+                        const int i = threadIdx.x + j * kPThreads;
+                        const unsigned long long w0 = dk0[i], w1 = dk1[i];
+                        put(o + __popcll(m[j] & below),
+                            make_uint4((uint32_t)w0, (uint32_t)(w0 >> 32), (uint32_t)w1, (uint32_t)(w1 >> 32)), c[j]);
+                    }
+                    o += __popcll(m[j]);
+                }
+            } else {
+                for (uint64_t d0 = beg + (uint64_t)wave * 64; d0 < end; d0 += kPThreads) {
+                    const uint64_t d = d0 + lane;
+                    const uint4 x = d < end ? data[d] : make_uint4(0, 0, 0, 0);
+                    const bool live = d < end && mine(x);
+                    const unsigned long long lm = __ballot(live);
+                    if (live) put(o + __popcll(lm & below), x, 1u);
+                    o += __popcll(lm);
+                }
+            }
+            __syncthreads();  // the table and wsum are free for the next class
+        }
+    }
+    block_add(&stat[1], wacc);
+}
+
+// every bucket's output becomes a whole number of 8-slot groups (16-B aligned sub rows): inert
+// descriptors of weight 0 up to the next multiple of 8 (capacities are multiples of 8)
+__global__ void __launch_bounds__(256) k_preagg_pad(uint4 *out, uint16_t *out_sub, uint32_t *out_w,
+                                                    const uint64_t *rbase, const uint64_t *rcap,
+                                                    const unsigned long long *rcur) {
+    const int b = threadIdx.x;
+    const uint64_t n = rcur[b];
+    if (n > rcap[b]) return;  // overflow: the host reports it
+    for (uint64_t z = n; z < ((n + 7) & ~7ull); ++z) {
+        out[rbase[b] + z] = make_uint4(0, 0, 0, 0);
+        out_sub[rbase[b] + z] = kDeadSub;
+        out_w[rbase[b] + z] = 0;
     }
 }
 
@@ -1838,6 +2085,188 @@ std::shared_ptr<NcBuckets> nc_ahead_end(NcAhead &a) {
     return a.bk;
 }
 
+// Pass B's plan over a bucket set (node_counter_bc, and the sender-side collapse of a sharded
+// build): the buckets' regions cut into chunks, every fine partition's offset (hfine / dfine, in
+// descriptors, runs padded to whole lines), and each chunk's run start per sub (druns).
+namespace {
+struct BPlan {
+    std::vector<uint64_t> bchunk;  // first chunk of each bucket (257 entries)
+    std::vector<uint64_t> hfine;   // fine-partition offsets (F + 1)
+    uint64_t nch = 0;
+    DevBuf<uint64_t> dcs, dfine;
+    DevBuf<uint32_t> dcl, dcb, druns;
+};
+
+void plan_b(mcaat_ctx *ctx, NcBuckets &bk, uint64_t n_desc, BPlan &pl) {
+    hipStream_t st = ctx->stream;
+    const int l2_bits = bk.l2_bits;
+    const uint32_t S = 1u << l2_bits;
+    const uint64_t F = 256ull * S;
+    std::vector<uint64_t> cstart;
+    std::vector<uint32_t> clen, cbucket;
+    std::vector<uint64_t> &bchunk = pl.bchunk;
+    bchunk.assign(257, 0);
+    for (int b = 0; b < 256; ++b) {
+        bchunk[b] = cstart.size();
+        for (const auto &rg : bk.regions[b])
+            for (uint64_t o = 0; o < rg.second; o += kChunk) {
+                cstart.push_back(rg.first + o);
+                clen.push_back((uint32_t)std::min<uint64_t>(kChunk, rg.second - o));
+                cbucket.push_back((uint32_t)b);
+            }
+    }
+    bchunk[256] = cstart.size();
+    const uint64_t nch = pl.nch = cstart.size();
+    DevBuf<uint64_t> &dcs = pl.dcs, &dfine = pl.dfine;
+    DevBuf<uint32_t> &dcl = pl.dcl, &dcb = pl.dcb, &druns = pl.druns;
+    dcs.alloc(nch ? nch : 1);
+    dfine.alloc(F + 1);
+    DevBuf<unsigned long long> dtot(F + 1);
+    dcl.alloc(nch ? nch : 1);
+    dcb.alloc(nch ? nch : 1);
+    HIP_OK(hipMemcpyAsync(dcs.p, cstart.data(), 8 * nch, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(dcl.p, clen.data(), 4 * nch, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(dcb.p, cbucket.data(), 4 * nch, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemsetAsync(dtot.p, 0, dtot.bytes(), st));
+    std::vector<uint64_t> &hfine = pl.hfine;
+    hfine.assign(F + 1, 0);
+    druns.alloc(nch * S ? nch * S : 1);  // per chunk and sub: count, then run start (lines)
+    {
+        KernelTimer kt(ctx, "l2_hist", 2.0 * (double)n_desc);
+        if (nch) {
+            hipLaunchKernelGGL(k_l2_hist, dim3((unsigned)nch), dim3(kBThreads), 4 * S, st, bk.sub.p, dcs.p, dcl.p, dcb.p,
+                               l2_bits, dtot.p, druns.p);
+            LAUNCH_OK();
+        }
+        exclusive_scan(ctx, (const uint64_t *)dtot.p, dfine.p, F + 1);
+        d2h(ctx, hfine.data(), dfine.p, 8 * (F + 1));
+        if (hfine[F] / kLG >= (1ull << 32)) throw Error(MCAAT_E_CAPACITY, "node_counter: 2^32 or more fine-partition lines");
+        if (nch) {
+            DevBuf<uint64_t> dbch(257);
+            HIP_OK(hipMemcpyAsync(dbch.p, bchunk.data(), 8 * 257, hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL(k_chunk_runs, dim3(grid_for(256ull * S, 256)), dim3(256), 0, st, druns.p,
+                               (const uint64_t *)dbch.p, (const uint64_t *)dfine.p, S);
+            LAUNCH_OK();
+            HIP_OK(hipStreamSynchronize(st));  // dbch is freed on scope exit
+        }
+        kt.stop();
+    }
+}
+}  // namespace
+
+// The sender-side collapse of a sharded build (dist.preagg; kernels: k_desc_preagg above). Pass B
+// runs unchanged over this rank's buckets, group by group under node_counter_bc's memory budget
+// (nc.group_budget), and each group's fine partitions collapse into the output region of their
+// L1 bucket. A region's capacity is its bucket's live descriptors (k_live_count) rounded up to 8
+// slots; the sub rows are written here, from each record's hash bits, so the owner's pass B
+// reads them as it reads pass A's.
+void node_counter_preagg(mcaat_ctx *ctx, NcBuckets &bk, int k, NcBuckets &out, uint64_t stats[4]) {
+    const int E = k + 1;
+    hipStream_t st = ctx->stream;
+    for (int i = 0; i < 4; ++i) stats[i] = 0;
+    out.l2_bits = bk.l2_bits;
+    out.n_occ = bk.n_occ;
+    out.base.clear();
+    out.regions.assign(256, {});
+    out.pre_slots.assign(256, 0);
+    uint64_t n_desc = 0;
+    for (int b = 0; b < 256; ++b)
+        for (const auto &rg : bk.regions[b]) {
+            out.pre_slots[b] += rg.second;
+            n_desc += rg.second;
+        }
+    if (n_desc == 0) {
+        out.data.alloc(1);
+        out.sub.alloc(8);
+        out.wgt.alloc(8);
+        bk.data.release();
+        bk.sub.release();
+        return;
+    }
+    const uint32_t S = 1u << bk.l2_bits;
+    const uint64_t F = 256ull * S;
+    BPlan plan;
+    plan_b(ctx, bk, n_desc, plan);
+    const std::vector<uint64_t> &hfine = plan.hfine;
+
+    // output regions: one per L1 bucket, its live descriptors rounded up to whole 8-slot groups
+    DevBuf<unsigned long long> dlive(256), dcur(256), dstat(2);
+    HIP_OK(hipMemsetAsync(dlive.p, 0, dlive.bytes(), st));
+    HIP_OK(hipMemsetAsync(dcur.p, 0, dcur.bytes(), st));
+    HIP_OK(hipMemsetAsync(dstat.p, 0, dstat.bytes(), st));
+    hipLaunchKernelGGL(k_live_count, dim3((unsigned)std::min<uint64_t>(plan.nch, (uint64_t)ctx->n_cu * 8)), dim3(kBlock), 0,
+                       st, bk.sub.p, plan.dcs.p, plan.dcl.p, plan.dcb.p, plan.nch, dlive.p);
+    LAUNCH_OK();
+    std::vector<unsigned long long> live(256), cur(256);
+    d2h(ctx, live.data(), dlive.p, 8 * 256);
+    std::vector<uint64_t> rbase(256), rcap(256);
+    uint64_t total = 0;
+    for (int b = 0; b < 256; ++b) {
+        rbase[b] = total;
+        rcap[b] = (live[b] + 7) & ~7ull;
+        total += rcap[b];
+        stats[0] += live[b];
+    }
+    DevBuf<uint64_t> drb(256), drc(256);
+    h2d(ctx, drb.p, rbase.data(), 8 * 256);
+    h2d(ctx, drc.p, rcap.data(), 8 * 256);
+    out.data.alloc(total ? total : 1);
+    out.sub.alloc(total ? total : 8);
+    out.wgt.alloc(total ? total : 8);
+
+    const uint32_t dmax = (uint32_t)std::min<int64_t>(kDMax, std::max<int64_t>(1, knob(ctx, "nc.desc_cap", kDMax)));
+    const uint32_t split_first = (uint32_t)std::min<int64_t>(kSplitMax, std::max<int64_t>(1, knob(ctx, "nc.split_first", kSplitLg)));
+    const uint32_t split_max = (uint32_t)std::min<int64_t>(kSplitMax, std::max<int64_t>(1, knob(ctx, "nc.split_max", kSplitMax)));
+    const uint64_t group_budget =
+        (uint64_t)knob(ctx, "nc.group_budget", (int64_t)std::max<uint64_t>(hfine[F] / 4 + 1, 1ULL << 28));  // descriptors per group
+    for (int b0 = 0; b0 < 256;) {
+        int b1 = b0 + 1;
+        while (b1 < 256 && hfine[(uint64_t)(b1 + 1) * S] - hfine[(uint64_t)b0 * S] <= group_budget) ++b1;
+        const uint64_t p0 = (uint64_t)b0 * S, p1 = (uint64_t)b1 * S;
+        const uint64_t gbase = hfine[p0], gn = hfine[p1] - gbase;
+        const uint64_t c0 = plan.bchunk[b0], c1 = plan.bchunk[b1];
+        if (gn) {
+            DevBuf<uint4> fine(gn);
+            {
+                KernelTimer kt(ctx, "preagg_partition", 34.0 * (double)gn);
+                hipLaunchKernelGGL(k_l2_scatter<false>, dim3((unsigned)(c1 - c0)), dim3(kBThreads), 0, st, bk.data.p, bk.sub.p,
+                                   plan.dcs.p + c0, plan.dcl.p + c0, (const uint32_t *)plan.druns.p + c0 * S, bk.l2_bits, E,
+                                   fine.p, gbase, (const uint32_t *)nullptr, (uint32_t *)nullptr);
+                LAUNCH_OK();
+                kt.stop();
+            }
+            {
+                KernelTimer kt(ctx, "desc_preagg", 16.0 * (double)gn);
+                const unsigned wg = (unsigned)std::min<uint64_t>(p1 - p0, (uint64_t)kCPerCu * ctx->n_cu);
+                hipLaunchKernelGGL(k_desc_preagg, dim3(wg), dim3(kPThreads), 0, st, fine.p, gbase, plan.dfine.p, p0, p1,
+                                   bk.l2_bits, out.data.p, out.sub.p, out.wgt.p, (const uint64_t *)drb.p,
+                                   (const uint64_t *)drc.p, dcur.p, dmax, split_first, split_max, dstat.p);
+                LAUNCH_OK();
+                kt.stop();  // waits for the launch: the group's buffer goes back after it
+            }
+        }
+        b0 = b1;
+    }
+    hipLaunchKernelGGL(k_preagg_pad, dim3(1), dim3(256), 0, st, out.data.p, out.sub.p, out.wgt.p, (const uint64_t *)drb.p,
+                       (const uint64_t *)drc.p, (const unsigned long long *)dcur.p);
+    LAUNCH_OK();
+    unsigned long long hs[2];
+    d2h(ctx, cur.data(), dcur.p, 8 * 256);
+    d2h(ctx, hs, dstat.p, 16);
+    for (int b = 0; b < 256; ++b) {
+        if (cur[b] > rcap[b]) throw Error(MCAAT_E_CAPACITY, "descriptor collapse: an output region overflowed");
+        if (cur[b]) out.regions[b].push_back({rbase[b], (cur[b] + 7) & ~7ull});
+        stats[1] += cur[b];
+    }
+    stats[2] = hs[0];
+    stats[3] = hs[1];
+    ctx->kstats["desc_preagg"].total_bytes += 22.0 * (double)stats[1];
+    bk.data.release();
+    bk.sub.release();
+    bk.regions.assign(256, {});
+    verbose_mark(ctx, "node_counter.preagg");
+}
+
 // passes B and C over the L1 buckets' regions (a bucket may hold several, e.g. one per rank
 // after a sharded build's descriptor exchange): final canonical counts of their edges
 void node_counter_bc(mcaat_ctx *ctx, NcBuckets &bk, int k, CountResult &out) {
@@ -1865,49 +2294,12 @@ void node_counter_bc(mcaat_ctx *ctx, NcBuckets &bk, int k, CountResult &out) {
     // The sub histogram of every chunk gives all fine-partition offsets at once; each group
     // then scatters its buckets into a buffer of its own and counts them, so the peak
     // footprint is the L1 buckets plus one group's fine partitions.
-    std::vector<uint64_t> cstart;
-    std::vector<uint32_t> clen, cbucket;
-    std::vector<uint64_t> bchunk(257, 0);  // first chunk of each bucket
-    for (int b = 0; b < 256; ++b) {
-        bchunk[b] = cstart.size();
-        for (const auto &rg : bk.regions[b])
-            for (uint64_t o = 0; o < rg.second; o += kChunk) {
-                cstart.push_back(rg.first + o);
-                clen.push_back((uint32_t)std::min<uint64_t>(kChunk, rg.second - o));
-                cbucket.push_back((uint32_t)b);
-            }
-    }
-    bchunk[256] = cstart.size();
-    const uint64_t nch = cstart.size();
-    DevBuf<uint64_t> dcs(nch ? nch : 1), dfine(F + 1);
-    DevBuf<unsigned long long> dtot(F + 1);
-    DevBuf<uint32_t> dcl(nch ? nch : 1), dcb(nch ? nch : 1);
-    HIP_OK(hipMemcpyAsync(dcs.p, cstart.data(), 8 * nch, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(dcl.p, clen.data(), 4 * nch, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(dcb.p, cbucket.data(), 4 * nch, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemsetAsync(dtot.p, 0, dtot.bytes(), st));
-    std::vector<uint64_t> hfine(F + 1);
-    DevBuf<uint32_t> druns(nch * S ? nch * S : 1);  // per chunk and sub: count, then run start (lines)
-    {
-        KernelTimer kt(ctx, "l2_hist", 2.0 * (double)n_desc);
-        if (nch) {
-            hipLaunchKernelGGL(k_l2_hist, dim3((unsigned)nch), dim3(kBThreads), 4 * S, st, l1s.p, dcs.p, dcl.p, dcb.p,
-                               P.l2_bits, dtot.p, druns.p);
-            LAUNCH_OK();
-        }
-        exclusive_scan(ctx, (const uint64_t *)dtot.p, dfine.p, F + 1);
-        d2h(ctx, hfine.data(), dfine.p, 8 * (F + 1));
-        if (hfine[F] / kLG >= (1ull << 32)) throw Error(MCAAT_E_CAPACITY, "node_counter: 2^32 or more fine-partition lines");
-        if (nch) {
-            DevBuf<uint64_t> dbch(257);
-            HIP_OK(hipMemcpyAsync(dbch.p, bchunk.data(), 8 * 257, hipMemcpyHostToDevice, st));
-            hipLaunchKernelGGL(k_chunk_runs, dim3(grid_for(256ull * S, 256)), dim3(256), 0, st, druns.p,
-                               (const uint64_t *)dbch.p, (const uint64_t *)dfine.p, S);
-            LAUNCH_OK();
-            HIP_OK(hipStreamSynchronize(st));  // dbch is freed on scope exit
-        }
-        kt.stop();
-    }
+    BPlan plan;
+    plan_b(ctx, bk, n_desc, plan);
+    const std::vector<uint64_t> &bchunk = plan.bchunk, &hfine = plan.hfine;
+    DevBuf<uint64_t> &dcs = plan.dcs, &dfine = plan.dfine;
+    DevBuf<uint32_t> &dcl = plan.dcl, &druns = plan.druns;
+    const bool weighted = bk.wgt.p != nullptr;  // (descriptor, multiplicity) records: dist.preagg
     const uint64_t n_live = hfine[F];
     verbose_mark(ctx, "node_counter.B_hist");
 
@@ -1949,6 +2341,7 @@ void node_counter_bc(mcaat_ctx *ctx, NcBuckets &bk, int k, CountResult &out) {
         int b0, b1;
         DevBuf<uint4> fine;
         hipEvent_t done = nullptr;
+        DevBuf<uint32_t> finew;  // weighted: the multiplicities at the same fine-partition slots
     };
     std::vector<Group> groups;
     for (int b0 = 0; b0 < 256;) {
@@ -1977,11 +2370,14 @@ void node_counter_bc(mcaat_ctx *ctx, NcBuckets &bk, int k, CountResult &out) {
         {
             AllocStreamScope scope(sb);  // written by pass B on the side stream
             g.fine.alloc(gn ? gn : 1);
+            if (weighted) g.finew.alloc(gn ? gn : 1);
         }
         auto *kt = new KernelTimer(ctx, "l2_partition", 34.0 * (double)gn, sb);  // sub rows + descriptors read, descriptors written
         if (c1 > c0) {
-            hipLaunchKernelGGL(k_l2_scatter, dim3((unsigned)(c1 - c0)), dim3(kBThreads), 0, sb, l1.p, l1s.p,
-                               dcs.p + c0, dcl.p + c0, (const uint32_t *)druns.p + c0 * S, P.l2_bits, E, g.fine.p, gbase);
+            hipLaunchKernelGGL(weighted ? k_l2_scatter<true> : k_l2_scatter<false>, dim3((unsigned)(c1 - c0)),
+                               dim3(kBThreads), 0, sb, l1.p, l1s.p, dcs.p + c0, dcl.p + c0,
+                               (const uint32_t *)druns.p + c0 * S, P.l2_bits, E, g.fine.p, gbase,
+                               (const uint32_t *)bk.wgt.p, g.finew.p);
             LAUNCH_OK();
         }
         kt->mark();
@@ -2010,13 +2406,17 @@ void node_counter_bc(mcaat_ctx *ctx, NcBuckets &bk, int k, CountResult &out) {
             {
                 KernelTimer kt(ctx, "lds_count", 16.0 * (double)gn);
                 const unsigned wg = (unsigned)std::min<uint64_t>(p1 - p0, (uint64_t)(tier == 2 ? 1 : kCPerCu) * ctx->n_cu);
-                auto kern = tier == 2 ? (prof_c ? k_lds_count<true, kCapBig, 1> : k_lds_count<false, kCapBig, 1>)
-                          : tier == 1 ? (prof_c ? k_lds_count<true, kCapMid, kCPerCu> : k_lds_count<false, kCapMid, kCPerCu>)
-                                : (prof_c ? k_lds_count<true, kCap, kCPerCu> : k_lds_count<false, kCap, kCPerCu>);
-                hipLaunchKernelGGL(kern, dim3(wg), dim3(kCThreads), 0, st, fine.p, gbase, dfine.p, p0, p1, E, out.keys.p,
+                auto kern_u = tier == 2 ? (prof_c ? k_lds_count<true, kCapBig, 1, false> : k_lds_count<false, kCapBig, 1, false>)
+                            : tier == 1 ? (prof_c ? k_lds_count<true, kCapMid, kCPerCu, false> : k_lds_count<false, kCapMid, kCPerCu, false>)
+                                  : (prof_c ? k_lds_count<true, kCap, kCPerCu, false> : k_lds_count<false, kCap, kCPerCu, false>);
+                auto kern_w = tier == 2 ? (prof_c ? k_lds_count<true, kCapBig, 1, true> : k_lds_count<false, kCapBig, 1, true>)
+                            : tier == 1 ? (prof_c ? k_lds_count<true, kCapMid, kCPerCu, true> : k_lds_count<false, kCapMid, kCPerCu, true>)
+                                  : (prof_c ? k_lds_count<true, kCap, kCPerCu, true> : k_lds_count<false, kCap, kCPerCu, true>);
+                hipLaunchKernelGGL(weighted ? kern_w : kern_u, dim3(wg), dim3(kCThreads), 0, st, fine.p, gbase, dfine.p, p0, p1, E, out.keys.p,
                                    out.counts.p, out_cap, dcnt.p, ovf_list.p, dcnt.p + 1,
                                    tier == 2 ? cap_max_big : tier == 1 ? cap_max_mid : cap_max, tier == 2 ? dmax_big : dmax,
-                                   dcnt.p + 2, tier == 2 ? split_big : split_first, split_max, prof_c ? dprof.p : nullptr);
+                                   dcnt.p + 2, tier == 2 ? split_big : split_first, split_max, prof_c ? dprof.p : nullptr,
+                                   (const uint32_t *)grp.finew.p);
                 LAUNCH_OK();
                 kt.stop();
             }
@@ -2033,8 +2433,9 @@ void node_counter_bc(mcaat_ctx *ctx, NcBuckets &bk, int k, CountResult &out) {
                 // global-table fallback for the partitions whose distinct edges overflowed LDS,
                 // in batches whose table fits a fixed memory budget
                 DevBuf<uint64_t> occ(n_ovf);
-                hipLaunchKernelGGL(k_part_occ, dim3((unsigned)std::min<uint64_t>(n_ovf, 65536)), dim3(kBlock), 0, st,
-                                   fine.p, gbase, dfine.p, ovf_list.p, n_ovf, occ.p);
+                hipLaunchKernelGGL(weighted ? k_part_occ<true> : k_part_occ<false>,
+                                   dim3((unsigned)std::min<uint64_t>(n_ovf, 65536)), dim3(kBlock), 0, st, fine.p, gbase,
+                                   dfine.p, ovf_list.p, n_ovf, occ.p, (const uint32_t *)grp.finew.p);
                 LAUNCH_OK();
                 std::vector<uint64_t> occ_h(n_ovf);
                 std::vector<uint32_t> parts_h(n_ovf);
@@ -2055,9 +2456,10 @@ void node_counter_bc(mcaat_ctx *ctx, NcBuckets &bk, int k, CountResult &out) {
                         HIP_OK(hipMemsetAsync(tab.p, 0, tab.bytes(), st));
                         HIP_OK(hipMemsetAsync(nn.p, 0, 8, st));
                         HIP_OK(hipMemsetAsync(dover.p, 0, 4, st));
-                        hipLaunchKernelGGL(k_fallback, dim3((unsigned)std::min<uint64_t>(q1 - q0, 65536)), dim3(kBlock),
-                                           0, st, fine.p, gbase, dfine.p, dparts.p, q1 - q0, E, tab.p, tcap - 1, nn.p,
-                                           dover.p);
+                        hipLaunchKernelGGL(weighted ? k_fallback<true> : k_fallback<false>,
+                                           dim3((unsigned)std::min<uint64_t>(q1 - q0, 65536)), dim3(kBlock), 0, st, fine.p,
+                                           gbase, dfine.p, dparts.p, q1 - q0, E, tab.p, tcap - 1, nn.p, dover.p,
+                                           (const uint32_t *)grp.finew.p);
                         LAUNCH_OK();
                         int over = 0;
                         HIP_OK(hipMemcpyAsync(&over, dover.p, 4, hipMemcpyDeviceToHost, st));
@@ -2131,6 +2533,7 @@ void node_counter_bc(mcaat_ctx *ctx, NcBuckets &bk, int k, CountResult &out) {
         }
         if (!overlap && gi + 1 < groups.size()) launch_b(groups[gi + 1]);
         fine.release();
+        grp.finew.release();
         event_put(ctx, grp.done);
         grp.done = nullptr;
     }
@@ -2147,6 +2550,7 @@ void node_counter_bc(mcaat_ctx *ctx, NcBuckets &bk, int k, CountResult &out) {
     }
     l1.release();
     l1s.release();
+    bk.wgt.release();
     bk.regions.assign(256, {});
     out.n = n_out;
     verbose_mark(ctx, "node_counter.C");

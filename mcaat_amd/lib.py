@@ -138,6 +138,7 @@ SIGNATURES = {
     "mcaat_reads_file_records": (C.c_int, [C.c_void_p, C.c_int, _u64p]),
     "mcaat_build_graph_sharded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
     "mcaat_cycle_finder_comm": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(_CfParams), C.POINTER(C.c_void_p)]),
+    "mcaat_desc_preaggregate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _u64p]),
     "mcaat_arena_check": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "mcaat_arena_usage": (C.c_int, [C.c_void_p, C.c_int, _u64p, _u64p, _u64p]),
     "mcaat_graph_shard_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), _u64p, _u64p]),
@@ -514,6 +515,15 @@ def count_edges(ctx: Context, reads: Reads, k: int) -> Tuple[np.ndarray, np.ndar
         ctx._lib.mcaat_free(C.cast(kp, C.c_void_p))
         ctx._lib.mcaat_free(C.cast(cp, C.c_void_p))
     return keys, counts
+
+
+def desc_preaggregate(ctx: Context, reads: Reads, k: int) -> dict:
+    """The sender-side collapse of a sharded build (knob dist.preagg) on one rank's reads, with no
+    communicator (mcaat_desc_preaggregate): live descriptors in, records out, records emitted raw,
+    and the sum of the emitted weights. Stage times: node_counter_a, shard_preagg."""
+    out = (C.c_uint64 * 4)()
+    _check(ctx._lib.mcaat_desc_preaggregate(ctx.h, reads.h, k, out))
+    return {"live_in": int(out[0]), "records_out": int(out[1]), "raw": int(out[2]), "weight_sum": int(out[3])}
 
 
 class Counts:
