@@ -103,12 +103,29 @@ __device__ __forceinline__ uint64_t canon_edge(uint64_t lsb, int E) {
 // ballot compaction as {first base, n edges, minimizer hash}; when a segment runs low on
 // room the wave fills in the bases of its entries and the workgroup scatters all segments
 // to the 256 L1 buckets.
-// 4 waves x 900-entry segments: ~52 KB of LDS, so three workgroups (12 waves, the VGPR
-// limit at 145 registers) share a CU and one's flush overlaps two others' scans (C3:
-// 87.6 -> 77.8 ms against 2 x 1500)
+// 4 waves x 1036-entry segments (900 with the bucket bytes, MCAAT_A1HASH=0): ~52 KB of LDS, so
+// three workgroups (12 waves, the VGPR limit at 168 registers) share a CU and one's flush
+// overlaps two others' scans (C3: 87.6 -> 77.8 ms against 2 x 1500)
+#ifndef MCAAT_AREG
+// 1: a lane holds its whole item in registers (fetched an item ahead, its leading s & 31 bases
+// shifted out once), so the step loop has no global load, no vmcnt wait and no per-lane 64-bit
+// shift; 0: the window words are loaded a step ahead
+#define MCAAT_AREG 1
+#endif
+#ifndef MCAAT_A1HASH
+// 1: the bucket phase overwrites a pre-entry's minimizer hash with its partition hash, so the
+// bucket (top byte) and the descriptor's hash bits come from the entry: one part_mix per
+// entry and no byte array of buckets; 0: bucket bytes in stage_l1, part_mix twice
+#define MCAAT_A1HASH 1
+#endif
 #ifndef MCAAT_AWAVES
 #define MCAAT_AWAVES 4
-#define MCAAT_ASEG 900
+#ifndef MCAAT_ASEG
+// 10 B of LDS per entry without the bucket bytes, 11 with them; 1036 entries are 53,752 B per
+// workgroup, the most that is three workgroups per CU whether the 160 KB are handed out in
+// 512-B or in 1280-B units
+#define MCAAT_ASEG (MCAAT_A1HASH ? 1036 : 900)
+#endif
 #define MCAAT_APERCU 3
 #endif
 #ifndef MCAAT_HASH
@@ -126,6 +143,13 @@ constexpr int kStage = kSeg * kAWaves;  // 8-B pre-entries
 static_assert(kAThreads >= 256, "threads < 256 own one L1 bucket each");
 static_assert(kSeg > 64 * kCk, "a segment must hold a worst-case step");
 static_assert(kStage <= 65536, "perm holds 16-bit stage indices");
+// k_sk_scatter's LDS: stage, perm (and stage_l1), sbase, hist/boff/bcur, rpos/rlim, rleft, wtot, more_flag
+constexpr int kALds = kStage * (8 + 2 + (MCAAT_A1HASH ? 0 : 1)) + kAWaves * 2 * 64 * 8 + 3 * 256 * 4 +
+                      2 * 256 * 8 + 256 * 4 + kAWaves * 4 + 2 * 4;
+static_assert(kALds <= 160 * 1024 / kAPerCu, "kAPerCu workgroups of pass A must fit a CU's LDS");
+constexpr int kItemRegs = 10;  // MCAAT_AREG: 32-bit registers holding an item's bases [0, 160)
+static_assert(kItem + 32 - 1 <= 160, "an item's bases (E <= 32) fit five 64-bit words");
+static_assert(16 * kItemRegs == 160 && kCk == 8, "a step's window starts at a register or half way into one");
 
 struct ItemSrc {
     const uint64_t *offsets;
@@ -136,6 +160,19 @@ struct ItemSrc {
     const uint32_t *item_np;
     uint64_t n_items;
 };
+
+// MCAAT_AREG: a wave-uniform value into a scalar register
+#if MCAAT_AREG
+__device__ __forceinline__ uint32_t uni(uint32_t x) { return __builtin_amdgcn_readfirstlane(x); }
+__device__ __forceinline__ int uni(int x) { return __builtin_amdgcn_readfirstlane(x); }
+__device__ __forceinline__ uint64_t uni64(uint64_t x) {
+    return ((uint64_t)uni((uint32_t)(x >> 32)) << 32) | uni((uint32_t)x);
+}
+#else
+__device__ __forceinline__ uint32_t uni(uint32_t x) { return x; }
+__device__ __forceinline__ int uni(int x) { return x; }
+__device__ __forceinline__ uint64_t uni64(uint64_t x) { return x; }
+#endif
 
 __device__ __forceinline__ void get_item(const ItemSrc &s, int E, uint64_t it, uint64_t &base, int &np) {
     if (s.fixed_len) {
@@ -273,7 +310,7 @@ constexpr uint16_t kDeadSub = 0xffff;  // sub-partition mark of an inert (n = 0)
 #ifndef MCAAT_APF
 #define MCAAT_APF 1
 #endif
-constexpr int kAPF = MCAAT_APF;  // scan steps of window words in flight (1 or 2)
+[[maybe_unused]] constexpr int kAPF = MCAAT_APF;  // scan steps of window words in flight (1 or 2)
 constexpr int kWB = MCAAT_WB;
 #ifndef MCAAT_WPIPE
 #define MCAAT_WPIPE 0
@@ -283,7 +320,8 @@ constexpr int kWB = MCAAT_WB;
 #endif
 constexpr bool kWPipe = MCAAT_WPIPE != 0;  // write phase: the next batch's loads before this batch's stores  // write batch (entries per thread per round: 3 loads each in flight)
 
-// 8-byte pre-entry of a closed super-k-mer: minimizer hash (low 32 bits); above it the
+// 8-byte pre-entry of a closed super-k-mer: minimizer hash (low 32 bits; MCAAT_A1HASH: the
+// flush's bucket phase puts the partition hash in its place); above it the
 // close position (7 bits), the first position (7), batch parity (1) and lane (6), all in
 // its item. The item's first base comes from the wave's table of the current and previous
 // batch (sbase), so the pre-entry is half a descriptor and the stage holds 1600 per wave;
@@ -300,7 +338,9 @@ __global__ void __launch_bounds__(kAThreads) k_sk_scatter(const uint64_t *__rest
                                                           unsigned long long *l1_cursor, uint16_t *__restrict__ l1_sub,
                                                           unsigned long long *prof, unsigned long long *rstate, int rmode) {
     __shared__ uint64_t stage[kStage];
+#if !MCAAT_A1HASH
     __shared__ uint8_t stage_l1[kStage];
+#endif
     __shared__ uint16_t perm[kStage];         // stage entries in bucket order
     __shared__ uint64_t sbase[kAWaves][2][64];  // item first base per (wave, batch parity, lane)
     __shared__ uint32_t hist[256];            // entries per bucket in this flush
@@ -340,7 +380,9 @@ __global__ void __launch_bounds__(kAThreads) k_sk_scatter(const uint64_t *__rest
     if (threadIdx.x == 0) more_flag[0] = more_flag[1] = 0;
     __syncthreads();
     uint64_t *seg = stage + __builtin_amdgcn_readfirstlane(wave * kSeg);  // wave-uniform: a scalar base
+#if !MCAAT_A1HASH
     uint8_t *seg_l1 = stage_l1 + wave * kSeg;
+#endif
     uint32_t nflush = 0;
 
     // absolute slot; a bucket whose region is exhausted drops the write (its cursor keeps
@@ -366,12 +408,47 @@ __global__ void __launch_bounds__(kAThreads) k_sk_scatter(const uint64_t *__rest
 
     // per-lane scan state (wave-uniform: active, c, ph, nck, fill, par, bsf)
     uint32_t H[3 * kCk];  // ring of three 8-hash groups; step c reads groups c, c+1, c+2 (mod 3)
+#if MCAAT_AREG
+    // the item's bases from 16 on, 16 per register (bases [0, 16) are only hashed when the item
+    // starts); every second step drops a register, so a step's window is always iw[0..2].
+    // nraw: the next batch's six words as loaded, (s1, np1) its items; (s2, np2) the batch
+    // after that one's, so neither the items nor the words are waited for where they are
+    // requested
+    uint32_t iw[kItemRegs - 1];
+    u64x2 nraw[3] = {{0, 0}, {0, 0}, {0, 0}};
+    uint64_t s1 = 0, s2 = 0;
+    int np1 = 0, np2 = 0;
+#pragma unroll
+    for (int i = 0; i < kItemRegs - 1; ++i) iw[i] = 0;
+#else
     uint64_t cw[3], pa = 0, pb = 0;  // the item's first words; the next step's window words
     uint64_t qa = 0, qb = 0;         // kAPF == 2: the step after next's
+#endif
     uint64_t s = 0;
     int np = 0, c = 0, ph = 0, nck = 0;
     uint32_t prev_hm = 0, h_open = 0, p7 = 0, ihc = 0, fill = 0, par = 1, bsf = 0;
     bool active = false;
+#if MCAAT_AREG
+    // items of batch bt (inactive lanes of a tail batch, and batches past the end: base 0, no
+    // position)
+    auto fetch_item = [&](uint64_t bt, uint64_t &sb, int &n) {
+        const uint64_t item = bt * 64 + lane;
+        sb = 0;
+        n = 0;
+        if (bt < n_batches && item < n_items) get_item(src, P.E, item, sb, n);
+    };
+    // the six words holding an item at base sb: s & 31 leading bases and at most
+    // kItem + 32 - 1 <= 160 of its own. The furthest word, (sb >> 5) + 5, lies inside the tail
+    // padding that every packed stream is allocated with (>= 16 words past its last base; a
+    // streamed part's region has 64); nothing is loaded for a batch past the end
+    auto fetch_words = [&](uint64_t bt, uint64_t sb) {
+        if (bt < n_batches) {
+            const u64x2 *w = (const u64x2 *)(packed + (sb >> 5));
+#pragma unroll
+            for (int k = 0; k < 3; ++k) nraw[k] = w[k];
+        }
+    };
+#else
     auto fetch = [&](uint64_t bt, uint64_t &sb, int &n, uint64_t *w) {
         const uint64_t item = bt * 64 + lane;
         sb = 0;
@@ -380,6 +457,7 @@ __global__ void __launch_bounds__(kAThreads) k_sk_scatter(const uint64_t *__rest
 #pragma unroll
         for (int k = 0; k < 3; ++k) w[k] = packed[(sb >> 5) + k];
     };
+#endif
 
     // one step: positions 8c .. 8c+7 of the lane's item; the window's bases start at 8c+16.
     // G = c mod 3 names the ring group holding positions 8c.. (compile time, so the ring
@@ -387,6 +465,18 @@ __global__ void __launch_bounds__(kAThreads) k_sk_scatter(const uint64_t *__rest
     auto step = [&](auto Gc) {
         constexpr int G = decltype(Gc)::value;
         c = __builtin_amdgcn_readfirstlane(c);
+#if MCAAT_AREG
+        // bases [8c + 16, 8c + 48): an even step's window is iw[0..1], an odd step's lies half
+        // a register further (a wave-uniform shift), and after it the registers move down by one
+        const uint32_t wsh = (uint32_t)(c & 1) * 16;
+        const uint64_t win = ((uint64_t)__builtin_amdgcn_alignbit(iw[2], iw[1], wsh) << 32) |
+                             __builtin_amdgcn_alignbit(iw[1], iw[0], wsh);
+        if (c & 1) {
+#pragma unroll
+            for (int i = 0; i + 1 < kItemRegs - 1; ++i) iw[i] = iw[i + 1];
+            iw[kItemRegs - 2] = 0;
+        }
+#else
         const int rb = kCk * c + 2 * kCk;
         const uint64_t win = win32(pa, pb, s + rb);
         if constexpr (kAPF == 2) {  // the step after next's window words; the next step's were loaded a step ago
@@ -400,6 +490,7 @@ __global__ void __launch_bounds__(kAThreads) k_sk_scatter(const uint64_t *__rest
             pa = nx.a;
             pb = nx.b;
         }
+#endif
         hash_step<kFull>(win, P.m, mmask, salt32, H + ((G + 2) % 3) * kCk);
         uint32_t hm[kCk];
         window_min<W, G>(H, hm);
@@ -472,11 +563,64 @@ __global__ void __launch_bounds__(kAThreads) k_sk_scatter(const uint64_t *__rest
     // a new item hashes its first two groups into the ring groups G, G+1
     auto start_item = [&](auto Gc) {
         constexpr int G = decltype(Gc)::value;
+#if MCAAT_AREG
+        // this batch's words were requested when the batch before it started, its items a
+        // batch earlier still; the leading s & 31 bases go out here, once (an alignbit by the
+        // lane's 2 * (s & 15) and a select on s & 16), so base j of the item is at bit
+        // 2 * (j & 15) of register j >> 4 in every lane
+        s = s1;
+        np = np1;
+        uint32_t it0;
+        {
+            const uint32_t h[12] = {(uint32_t)nraw[0].a, (uint32_t)(nraw[0].a >> 32), (uint32_t)nraw[0].b,
+                                    (uint32_t)(nraw[0].b >> 32), (uint32_t)nraw[1].a, (uint32_t)(nraw[1].a >> 32),
+                                    (uint32_t)nraw[1].b, (uint32_t)(nraw[1].b >> 32), (uint32_t)nraw[2].a,
+                                    (uint32_t)(nraw[2].a >> 32), (uint32_t)nraw[2].b, (uint32_t)(nraw[2].b >> 32)};
+            const uint32_t lsh = 2 * ((uint32_t)s & 15);
+            const bool up = ((uint32_t)s & 16) != 0;
+            uint32_t t[kItemRegs + 1];
+#pragma unroll
+            for (int i = 0; i < kItemRegs + 1; ++i) t[i] = __builtin_amdgcn_alignbit(h[i + 1], h[i], lsh);
+            it0 = up ? t[1] : t[0];
+#pragma unroll
+            for (int i = 0; i < kItemRegs - 1; ++i) iw[i] = up ? t[i + 2] : t[i + 1];
+        }
+        // The requests below must land in the registers that carry them round the loop: a load
+        // into a temporary is copied at the end of this block, and the copy waits for the load.
+        // The compiler places the copies of a rotation (s1 = s2) at the end of the block, behind
+        // the load that refills s2, so the three moves are written out; with them the item's
+        // registers become values of their own, which ends the old words' lives, and no load
+        // moves above this point
+        static_assert(kItemRegs == 10, "the operand list below names every item register");
+        {
+            uint32_t lo, hi;
+            asm volatile("v_mov_b32 %0, %12\n\tv_mov_b32 %1, %13\n\tv_mov_b32 %2, %14"
+                         : "=&v"(lo), "=&v"(hi), "=&v"(np1), "+v"(it0), "+v"(iw[0]), "+v"(iw[1]), "+v"(iw[2]),
+                           "+v"(iw[3]), "+v"(iw[4]), "+v"(iw[5]), "+v"(iw[6]), "+v"(iw[7])
+                         : "v"((uint32_t)s2), "v"((uint32_t)(s2 >> 32)), "v"(np2), "v"(iw[8]));
+            s1 = ((uint64_t)hi << 32) | lo;
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        fetch_words(batch + bstride, s1);
+        fetch_item(batch + 2 * bstride, s2, np2);
+#else
         fetch(batch, s, np, cw);
+#endif
         par ^= 1u;
         ++bsf;
         sbase[wave][par][lane] = s;
         ihc = (par << kPePar) | ((uint32_t)lane << kPeLane);
+        int mx = np;
+#pragma unroll
+        for (int o = 32; o; o >>= 1) mx = max(mx, __shfl_xor(mx, o));
+        nck = uni(mx / kCk + 1);  // steps covering positions 0..max np (the last close)
+#if MCAAT_AREG
+        // bases [0, 32) and [8, 40)
+        hash_step<kFull>(((uint64_t)iw[0] << 32) | it0, P.m, mmask, salt32, H + G * kCk);
+        hash_step<kFull>(((uint64_t)__builtin_amdgcn_alignbit(iw[1], iw[0], 16) << 32) |
+                             __builtin_amdgcn_alignbit(iw[0], it0, 16),
+                         P.m, mmask, salt32, H + ((G + 1) % 3) * kCk);
+#else
         {
             const u64x2 nx = *(const u64x2 *)(packed + ((s + 2 * kCk) >> 5));
             pa = nx.a;
@@ -487,30 +631,30 @@ __global__ void __launch_bounds__(kAThreads) k_sk_scatter(const uint64_t *__rest
             qa = nx.a;
             qb = nx.b;
         }
-        int mx = np;
-#pragma unroll
-        for (int o = 32; o; o >>= 1) mx = max(mx, __shfl_xor(mx, o));
-        nck = mx / kCk + 1;  // steps covering positions 0..max np (the last close)
         const int o8 = (int)(s & 31) + kCk;
         hash_step<kFull>(win32(cw[0], cw[1], s), P.m, mmask, salt32, H + G * kCk);
         hash_step<kFull>(o8 >= 32 ? win32(cw[1], cw[2], s + kCk) : win32(cw[0], cw[1], s + kCk), P.m, mmask,
                          salt32, H + ((G + 1) % 3) * kCk);
+#endif
         c = 0;
         active = true;
     };
     // false: the wave goes to the flush with its ring at phase G
     auto run = [&](auto Gc) -> bool {
         constexpr int G = decltype(Gc)::value;
-        if (!active) {
+        // (the scan's branches are on scalar conditions: values merged at a divergent join are
+        // copied there, and a copy of the words just requested would wait for them)
+        batch = uni64(batch);
+        if (!uni((int)active)) {
             // no more items, or the segment already references two batches (the sbase slots)
-            if (batch >= n_batches || bsf >= 2) {
+            if (batch >= n_batches || uni(bsf) >= 2) {
                 ph = G;
                 return false;
             }
             start_item(Gc);
         }
         // a wave short of room for a worst-case step goes to the flush
-        if (fill + 64 * kCk > (uint32_t)kSeg) {
+        if (uni(fill) + 64 * kCk > (uint32_t)kSeg) {
             ph = G;
             return false;
         }
@@ -522,6 +666,11 @@ __global__ void __launch_bounds__(kAThreads) k_sk_scatter(const uint64_t *__rest
         return true;
     };
 
+#if MCAAT_AREG
+    fetch_item(batch, s1, np1);
+    fetch_words(batch, s1);
+    fetch_item(batch + bstride, s2, np2);
+#endif
     for (;;) {
         // the scan is unrolled over the three ring phases; a flush may interrupt it at any
         // phase, so the ring is rotated back to phase 0 first (once per flush)
@@ -547,11 +696,23 @@ __global__ void __launch_bounds__(kAThreads) k_sk_scatter(const uint64_t *__rest
         tick(0);
         // bucket of each entry: the minimum hash is biased towards 0, so buckets come from
         // a re-hash of it (a bijection)
+#if MCAAT_A1HASH
+        // the partition hash takes the minimizer hash's place in the entry (nothing after this
+        // reads the latter): the permutation pass and the write phase take the bucket and the
+        // descriptor's hash bits from it
+        for (uint32_t e = lane; e < fill; e += 64) {
+            uint32_t *lo = (uint32_t *)(seg + e);
+            const uint32_t pm = part_mix(*lo);
+            *lo = pm;
+            atomicAdd(&hist[pm >> 24], 1u);
+        }
+#else
         for (uint32_t e = lane; e < fill; e += 64) {
             const uint32_t l1 = part_mix((uint32_t)seg[e]) >> 24;
             seg_l1[e] = (uint8_t)l1;
             atomicAdd(&hist[l1], 1u);
         }
+#endif
         tick(1);
         if (lane == 0) wtot[wave] = fill;
         if (lane == 0 && (active || batch < n_batches)) more_flag[nflush & 1] = 1;
@@ -595,7 +756,11 @@ __global__ void __launch_bounds__(kAThreads) k_sk_scatter(const uint64_t *__rest
         if (tb < 256) hist[tb] = 0;
         tick(3);
         for (uint32_t e = lane; e < fill; e += 64) {
+#if MCAAT_A1HASH
+            const int b = (int)(*(const uint32_t *)(seg + e) >> 24);
+#else
             const int b = seg_l1[e];
+#endif
             perm[boff[b] + atomicAdd(&bcur[b], 1u)] = (uint16_t)(wave * kSeg + e);
         }
         lds_barrier();  // C: perm ready
@@ -637,8 +802,13 @@ __global__ void __launch_bounds__(kAThreads) k_sk_scatter(const uint64_t *__rest
             for (int k = 0; k < kWB; ++k) {
                 const uint32_t j = j0 + k * kAThreads;
                 if (j >= total) continue;
+#if MCAAT_A1HASH
+                const uint32_t h = (uint32_t)q[S][k];  // the partition hash (bucket phase)
+                const int b = (int)(h >> 24);
+#else
                 const uint32_t i = perm[j];
                 const int b = stage_l1[i];
+#endif
                 const uint32_t hi = (uint32_t)(q[S][k] >> 32);
                 const uint32_t n = (hi & 127) - ((hi >> kPeP) & 127);
                 const int sh = 2 * (int)(B0[S][k] & 31);
@@ -648,7 +818,9 @@ __global__ void __launch_bounds__(kAThreads) k_sk_scatter(const uint64_t *__rest
                 const uint64_t w0 = (sh ? (x[S][k][0] >> sh) | (x[S][k][1] << (64 - sh)) : x[S][k][0]) & mask_bits(2 * L);
                 uint64_t w1 = (sh ? (x[S][k][1] >> sh) | (x[S][k][2] << (64 - sh)) : x[S][k][1]) &
                               mask_bits(L > 32 ? 2 * (L - 32) : 0);
+#if !MCAAT_A1HASH
                 const uint32_t h = part_mix((uint32_t)q[S][k]);
+#endif
                 w1 |= ((uint64_t)n << kNShift) | ((uint64_t)((h >> (24 - kHBits)) & ((1u << kHBits) - 1)) << kHShift);
                 put(b, rpos[b] + (j - boff[b]),
                     make_uint4((uint32_t)w0, (uint32_t)(w0 >> 32), (uint32_t)w1, (uint32_t)(w1 >> 32)));
