@@ -293,6 +293,11 @@ int mcaat_comm_schedule_check(int world, uint64_t seed, uint64_t piece_bytes, ui
  * in/out: {w0, w1}; w1 = bases [32,54) in bits 0..43 | n edges at 44 | hash bits at 50.
  * MCAAT_E_INVALID unless 1 <= E <= 31 and n + E - 1 <= 54. No GPU. */
 int mcaat_desc_canonical(const uint64_t in[2], int E, uint64_t out[2]);
+/* Host-only: whether a descriptor's second word w1 marks a live descriptor (n > 0), and its fine
+ * sub-partition for l2_bits sub bits (csrc/desc_canon.h desc_live and desc_sub, the functions
+ * node_counter's passes A and B run on the device). MCAAT_E_INVALID unless 0 <= l2_bits <= 14.
+ * No GPU. */
+int mcaat_desc_sub(uint64_t w1, int l2_bits, int *live, uint32_t *sub);
 int mcaat_comm_barrier(mcaat_comm *c);
 /* host memory: sizes[world] = every rank's byte count; then the bytes in rank order */
 int mcaat_comm_allgather_sizes(mcaat_comm *c, uint64_t bytes, uint64_t *sizes);
@@ -418,7 +423,11 @@ int mcaat_set_knob(mcaat_ctx *ctx, const char *name, int64_t value);
  *   dist.adj_chunk    sharded adjacency: edges per request/response exchange (default 2^26)
  *   dist.dir_edges    sharded adjacency: edges per prefix of the range's radix directory (default 2)
  *   nc.a_mini         pass A's slots per (workgroup, L1 bucket) reservation (default 1024 on one GPU,
- *                      256 for a rank of a sharded build; rounded down to a multiple of 8)
+ *                      256 for a rank of a sharded build; rounded down to a multiple of 8, at most 2^16)
+ *   nc.a_adapt        0: every pass A reservation has nc.a_mini slots (default 1: a workgroup near the
+ *                      end of its input reserves twice its expected need plus 64 slots)
+ *   nc.a_stats        1: pass A counts its slots; mcaat_kernel_timing reports them as the launch counts
+ *                      of a_slots_reserved, a_slots_live, a_slots_dead_switch and a_slots_dead_end
  *   dist.bfs_sync     1: the region BFS (candidates' forward region, FindCycle's backward region)
  *                      runs one routed exchange with host waits per hop, and the FindCycle reach on
  *                      the search replica reads its frontier size after every hop (round 5's forms;

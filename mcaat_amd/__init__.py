@@ -18,6 +18,7 @@ from .lib import (  # noqa: F401
     count_edges,
     desc_canonical,
     desc_preaggregate,
+    desc_sub,
     edges_reduce,
     device_count,
     load_library,

@@ -1097,7 +1097,7 @@ int mcaat_set_knob(mcaat_ctx *ctx, const char *name, int64_t value) {
         "fq.hostpack",     "sort.mid_counting", "nc.big_table", "cf.fused_init", "sort.mid_occ", "cf.scan_u", "cf.prep_batch", "cf.dls_lanes", "dist.oriented",
         "sort.small_mid", "sort.small_limit", "cf.recount", "cf.dls_host",
         "dist.desc",      "cf.compact",         "cf.fresh",   "cf.dls_persist", "nc.split_first", "nc.split_max", "cf.pull_flags", "cf.dls_budget", "nc.grow_early",
-        "nc.free_sync", "dist.shard_cf", "dist.ruler_mask", "dist.adj_chunk", "dist.dir_edges", "nc.ahead", "dist.adj_ranges", "dist.win_ranges", "cf.dls_lds", "cf.dls_lds_cap", "dist.segs_at_one", "nc.a_mini", "dist.bfs_sync", "cf.compact_pct", "dist.bfs_block", "dist.bfs_frontier", "dist.res_fixed", "dist.res_batch", "dist.res_block_mb", "dist.walk_block", "dist.walk_batch", "dist.grid_blocks", "dist.preagg"};
+        "nc.free_sync", "dist.shard_cf", "dist.ruler_mask", "dist.adj_chunk", "dist.dir_edges", "nc.ahead", "dist.adj_ranges", "dist.win_ranges", "cf.dls_lds", "cf.dls_lds_cap", "dist.segs_at_one", "nc.a_mini", "nc.a_adapt", "nc.a_stats", "dist.bfs_sync", "cf.compact_pct", "dist.bfs_block", "dist.bfs_frontier", "dist.res_fixed", "dist.res_batch", "dist.res_block_mb", "dist.walk_block", "dist.walk_batch", "dist.grid_blocks", "dist.preagg"};
     return guarded([&] {
         require(ctx && name, "null argument");
         bool ok = false;
@@ -1132,6 +1132,15 @@ int mcaat_desc_canonical(const uint64_t in[2], int E, uint64_t out[2]) {
         desc_canonical(w0, w1, E);
         out[0] = w0;
         out[1] = w1;
+    });
+}
+
+int mcaat_desc_sub(uint64_t w1, int l2_bits, int *live, uint32_t *sub) {
+    return guarded([&] {
+        require(live && sub, "null argument");
+        require(l2_bits >= 0 && l2_bits <= kHBits, "l2_bits must be in [0, 14]");
+        *live = desc_live(w1) ? 1 : 0;
+        *sub = desc_sub(w1, l2_bits);
     });
 }
 

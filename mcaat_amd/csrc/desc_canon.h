@@ -31,6 +31,16 @@ constexpr int kHBits = 14;
 // kept.
 static_assert(kDescBases < 64, "a canonical descriptor's w0 is never all ones only while L < 64");
 
+// A descriptor is live when it holds at least one edge; padding and zero-filled slots have n = 0.
+MCAAT_DESC_HD bool desc_live(uint64_t w1) { return ((w1 >> kNShift) & 63) != 0; }
+
+// The fine sub-partition of a descriptor inside its L1 bucket: the top l2_bits of the hash bits,
+// which are the top bits of w1 (0 <= l2_bits <= kHBits; no bits: sub 0).
+static_assert(kHShift + kHBits == 64, "the hash bits end at the top of w1");
+MCAAT_DESC_HD uint32_t desc_sub(uint64_t w1, int l2_bits) {
+    return l2_bits > 0 ? (uint32_t)(w1 >> (64 - l2_bits)) : 0u;
+}
+
 // reverse the 2-bit groups of a word: the hardware bit reverse plus one swap of adjacent bits
 #if defined(__has_builtin)
 #if __has_builtin(__builtin_bitreverse32)

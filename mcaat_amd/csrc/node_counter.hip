@@ -54,6 +54,10 @@ struct SkParams {
     int l2_bits;  // hash bits after the 8 L1 bits used for fine partitions
     uint64_t salt;
     uint32_t mini;  // slots per reservation (a multiple of 8: every region starts 16-B aligned in the sub rows)
+    // reservations sized by the work a workgroup has left (knob nc.a_adapt; 0: always `mini`):
+    // expected entries per batch of 64 items and L1 bucket, in 1/256
+    uint32_t a_epb;
+    uint32_t a_far;  // batches a wave has to have left to expect two full-size reservations filled
 };
 
 __device__ __forceinline__ uint64_t desc_window(uint64_t w0, uint64_t w1, int i, int E) {
@@ -302,6 +306,15 @@ __device__ __forceinline__ void window_min(const uint32_t *H, uint32_t *hm) {
 // at 256 (more reservation atomics); knob nc.a_mini sets it
 constexpr uint32_t kMiniOne = 1024, kMiniShard = 256;
 constexpr uint16_t kDeadSub = 0xffff;  // sub-partition mark of an inert (n = 0) slot
+// a prefetched reservation in rstate (streamed input): its offset in the low bits, its size above
+constexpr int kResShift = 44;
+constexpr unsigned long long kResMask = (1ull << kResShift) - 1;
+constexpr uint32_t kMiniMax = 1u << 16;  // largest reservation (nc.a_mini)
+// adaptive reservations: quarters of the expected need to reserve (8: twice the need), plus 64 slots
+#ifndef MCAAT_AADAPTQ
+#define MCAAT_AADAPTQ 8
+#endif
+constexpr uint32_t kAdaptQ = MCAAT_AADAPTQ;
 
 
 #ifndef MCAAT_WB
@@ -336,7 +349,8 @@ __global__ void __launch_bounds__(kAThreads) k_sk_scatter(const uint64_t *__rest
                                                           const uint64_t *__restrict__ l1_base,
                                                           const uint64_t *__restrict__ l1_cap,
                                                           unsigned long long *l1_cursor, uint16_t *__restrict__ l1_sub,
-                                                          unsigned long long *prof, unsigned long long *rstate, int rmode) {
+                                                          unsigned long long *prof, unsigned long long *rstate, int rmode,
+                                                          unsigned long long *dstat) {
     __shared__ uint64_t stage[kStage];
 #if !MCAAT_A1HASH
     __shared__ uint8_t stage_l1[kStage];
@@ -358,11 +372,32 @@ __global__ void __launch_bounds__(kAThreads) k_sk_scatter(const uint64_t *__rest
     // the next one, requested a flush ahead so the cursor atomic's latency is hidden
     // (the atomic's result stays unused until the next flush, so its latency is hidden)
     unsigned long long my_next = 0, my_base = 0;
+    uint32_t my_nsz = 0;     // slots of the reservation at my_next
     uint32_t prev_need = 0;  // applied to rpos/rleft at the next flush (after its barrier)
     // rmode (one launch per part of a streamed input, nc_ahead_*): 0 a single launch; 1 the
     // first of several, 2 a middle one, 3 the last. After 1 and 2 every workgroup leaves its
     // reservations in rstate (no inert fill) and the next launch (same grid) takes them up
     unsigned long long *rs = rstate ? rstate + ((uint64_t)blockIdx.x * 256 + (tb & 255)) * 3 : nullptr;
+    const uint64_t n_items = src.fixed_len ? src.n_reads * src.ipr : src.n_items;
+    const uint64_t n_batches = (n_items + 63) / 64;
+    const uint64_t bstride = (uint64_t)gridDim.x * kAWaves;
+    uint64_t batch = (uint64_t)blockIdx.x * kAWaves + wave;
+    // Slots of the next reservation, requested while `in_hand` slots of the current one are
+    // still free. While the workgroup expects to fill both (its waves have a_far batches or more
+    // to come) that is P.mini; near the end of the input it is kAdaptQ / 4 times the expected
+    // need beyond the slots in hand, plus 64 (a multiple of 8, at most P.mini), so that what the
+    // end of the kernel fills with inert slots is small. An underestimate costs a synchronous
+    // grab. Only a launch that sees the end of the input adapts (rmode 0 and 3)
+    const bool adapt = P.a_epb != 0 && (rmode == 0 || rmode == 3);
+    const uint64_t far_span = (uint64_t)P.a_far * bstride;
+    auto next_size = [&](uint32_t in_hand) -> uint32_t {
+        if (!adapt || batch + far_span <= n_batches) return P.mini;
+        const uint64_t rem = batch < n_batches ? (n_batches - batch + bstride - 1) / bstride : 0;
+        const uint64_t expect = (rem * kAWaves * P.a_epb) >> 8;
+        const uint64_t beyond = expect > in_hand ? expect - in_hand : 0;
+        if (beyond >= P.mini) return P.mini;
+        return min(P.mini, ((uint32_t)(beyond * kAdaptQ / 4) + 64 + 7) & ~7u);
+    };
     if (tb < 256) {
         hist[tb] = 0;
         bcur[tb] = 0;
@@ -371,10 +406,12 @@ __global__ void __launch_bounds__(kAThreads) k_sk_scatter(const uint64_t *__rest
         if (rmode >= 2) {
             rpos[tb] = rs[0];
             rleft[tb] = (uint32_t)rs[1];
-            my_next = rs[2];
+            my_next = rs[2] & kResMask;  // the reservation's size travels in the high bits
+            my_nsz = (uint32_t)(rs[2] >> kResShift);
         } else {
             rleft[tb] = 0;
-            my_next = atomicAdd(&l1_cursor[tb], (unsigned long long)P.mini);
+            my_nsz = next_size(0);
+            my_next = atomicAdd(&l1_cursor[tb], (unsigned long long)my_nsz);
         }
     }
     if (threadIdx.x == 0) more_flag[0] = more_flag[1] = 0;
@@ -388,19 +425,14 @@ __global__ void __launch_bounds__(kAThreads) k_sk_scatter(const uint64_t *__rest
     // absolute slot; a bucket whose region is exhausted drops the write (its cursor keeps
     // counting, so the host re-sizes and re-runs). Beside each descriptor goes its fine
     // sub-partition (kDeadSub for padding), so pass B's counting passes read 2 bytes, not 16.
-    const int sub_shift = kHShift + kHBits - P.l2_bits;
     auto put = [&](int b, uint64_t pos, const uint4 &d) {
         if (pos < rlim[b]) {
             l1_data[pos] = d;
             const uint64_t hi = (uint64_t)d.w << 32;
-            l1_sub[pos] = ((d.w >> (kNShift - 32)) & 63) ? (uint16_t)(sub_shift < 64 ? hi >> sub_shift : 0) : kDeadSub;
+            l1_sub[pos] = desc_live(hi) ? (uint16_t)desc_sub(hi, P.l2_bits) : kDeadSub;
         }
     };
 
-    const uint64_t n_items = src.fixed_len ? src.n_reads * src.ipr : src.n_items;
-    const uint64_t n_batches = (n_items + 63) / 64;
-    const uint64_t bstride = (uint64_t)gridDim.x * kAWaves;
-    uint64_t batch = (uint64_t)blockIdx.x * kAWaves + wave;
     constexpr bool kFull = FULL;  // m == 16: the m-mers need no mask
     const uint32_t mmask = (uint32_t)mask_bits(2 * P.m);
     const uint32_t salt32 = (uint32_t)P.salt;
@@ -728,12 +760,14 @@ __global__ void __launch_bounds__(kAThreads) k_sk_scatter(const uint64_t *__rest
             const uint32_t need = hist[tb];
             if (need > rleft[tb]) {
                 for (uint32_t z = 0; z < rleft[tb]; ++z) put(tb, rpos[tb] + z, make_uint4(0, 0, 0, 0));
-                if (need <= P.mini) {
+                if (dstat && rleft[tb]) atomicAdd(&dstat[1], (unsigned long long)rleft[tb]);
+                if (need <= my_nsz) {
                     rpos[tb] = my_base + my_next;
-                    rleft[tb] = P.mini;
-                    my_next = atomicAdd(&l1_cursor[tb], (unsigned long long)P.mini);
-                } else {  // more than a reservation in one flush: grab synchronously
-                    const uint32_t grab = ((need + P.mini - 1) / P.mini) * P.mini;
+                    rleft[tb] = my_nsz;
+                    my_nsz = next_size(my_nsz - need);
+                    my_next = atomicAdd(&l1_cursor[tb], (unsigned long long)my_nsz);
+                } else {  // more than the next reservation in one flush: grab synchronously
+                    const uint32_t grab = ((need + my_nsz - 1) / my_nsz) * my_nsz;
                     rpos[tb] = my_base + atomicAdd(&l1_cursor[tb], (unsigned long long)grab);
                     rleft[tb] = grab;
                 }
@@ -769,6 +803,7 @@ __global__ void __launch_bounds__(kAThreads) k_sk_scatter(const uint64_t *__rest
         uint32_t total = 0;
 #pragma unroll
         for (int w = 0; w < kAWaves; ++w) total += wtot[w];
+        if (dstat && threadIdx.x == 0 && total) atomicAdd(&dstat[0], (unsigned long long)total);
         // a batch of kWB entries per thread: first its stage reads and base loads, then the
         // descriptors; with kWPipe the next batch's loads are issued before this batch's
         // descriptors are built (two batches of registers, slots fixed at compile time)
@@ -862,18 +897,19 @@ __global__ void __launch_bounds__(kAThreads) k_sk_scatter(const uint64_t *__rest
         if (tb < 256) {
             rs[0] = rpos[tb];
             rs[1] = rleft[tb];
-            rs[2] = my_next;
+            rs[2] = my_next | ((unsigned long long)my_nsz << kResShift);
         }
         return;
     }
     __syncthreads();
     for (int pass = 0; pass < 2; ++pass) {
+        if (dstat && tb < 256 && rleft[tb]) atomicAdd(&dstat[2], (unsigned long long)rleft[tb]);
         for (int b = 0; b < 256; ++b)
             for (uint32_t z = threadIdx.x; z < rleft[b]; z += kAThreads) put(b, rpos[b] + z, make_uint4(0, 0, 0, 0));
         __syncthreads();
         if (tb < 256) {
             rpos[tb] = my_base + my_next;
-            rleft[tb] = P.mini;
+            rleft[tb] = my_nsz;
         }
         __syncthreads();
     }
@@ -882,7 +918,8 @@ __global__ void __launch_bounds__(kAThreads) k_sk_scatter(const uint64_t *__rest
 }
 
 typedef void (*SkKernel)(const uint64_t *, ItemSrc, SkParams, uint4 *, const uint64_t *, const uint64_t *,
-                         unsigned long long *, uint16_t *, unsigned long long *, unsigned long long *, int);
+                         unsigned long long *, uint16_t *, unsigned long long *, unsigned long long *, int,
+                         unsigned long long *);
 SkKernel sk_kernel(int w, bool full) {
     if (full) {
         switch (w) {
@@ -910,7 +947,15 @@ SkKernel sk_kernel(int w, bool full) {
 // exclusive scan those are the fine-partition bases, and k_l2_scatter reserves space per
 // (workgroup, sub) with one atomic on the fine cursor and ranks inside the workgroup in LDS.
 constexpr int kBThreads = 1024;
-constexpr uint32_t kChunk = 65536;
+// descriptors per pass B workgroup (build option MCAAT_BCHUNK). Each (chunk, sub) run is padded
+// to whole lines, so the padding halves with each doubling, and so does the number of
+// workgroups that share the GPU. Chunk lengths, ranks inside a chunk and run starts (in lines,
+// checked against 2^32 in plan_b) are 32-bit, which holds for any chunk below 2^31.
+#ifndef MCAAT_BCHUNK
+#define MCAAT_BCHUNK 65536
+#endif
+constexpr uint32_t kChunk = MCAAT_BCHUNK;
+static_assert(kChunk >= 8 && kChunk % 8 == 0 && kChunk <= (1u << 24), "chunks start on 16-B aligned sub rows");
 
 
 // Every (chunk, sub) run is rounded up to a multiple of 4 descriptors (64 B) and padded
@@ -1003,7 +1048,6 @@ constexpr bool kCoopFlush = MCAAT_BCOOP != 0;  // completed lines written by the
 // buffers stay descriptors only: 128 KB of the 160); line padding gets weight 0.
 template <bool WEIGHTED>
 __global__ void __launch_bounds__(kBThreads) k_l2_scatter(const uint4 *__restrict__ data,
-                                                          const uint16_t *__restrict__ sub,
                                                           const uint64_t *chunk_start, const uint32_t *chunk_len,
                                                           const uint32_t *runs, int l2_bits, int E,
                                                           uint4 *__restrict__ out, uint64_t gbase,
@@ -1023,13 +1067,14 @@ __global__ void __launch_bounds__(kBThreads) k_l2_scatter(const uint4 *__restric
     __syncthreads();
     const uint64_t s0 = chunk_start[c];
     const uint32_t n = chunk_len[c];
-    // one descriptor per thread per round, the next kBPF rounds' already in flight
-    uint32_t v[kBPF];
+    // one descriptor per thread per round, the next kBPF rounds' already in flight. Liveness and
+    // the sub come from the descriptor itself (desc_live, desc_sub: what pass A put into the sub
+    // rows, which only the counting passes read); a lane past the chunk's end holds a zero
+    // descriptor, which is dead
     uint4 d[kBPF];
 #pragma unroll
     for (int j = 0; j < kBPF; ++j) {
         const uint32_t i = j * kBThreads + threadIdx.x;
-        v[j] = i < n ? sub[s0 + i] : kDeadSub;
         d[j] = i < n ? data[s0 + i] : make_uint4(0, 0, 0, 0);
     }
     for (uint32_t i00 = 0; i00 < n; i00 += kBPF * kBThreads)
@@ -1037,12 +1082,12 @@ __global__ void __launch_bounds__(kBThreads) k_l2_scatter(const uint4 *__restric
     for (int j = 0; j < kBPF; ++j) {
         const uint32_t i0 = i00 + j * kBThreads;
         if (i0 >= n) break;  // uniform: every thread reaches the same barriers
-        const uint32_t cv = v[j];
         uint4 cd = d[j];
         const uint32_t ni = i0 + kBPF * kBThreads + threadIdx.x;
-        v[j] = ni < n ? sub[s0 + ni] : kDeadSub;
-        if (ni < n) d[j] = data[s0 + ni];
-        const bool live = cv != kDeadSub;
+        d[j] = ni < n ? data[s0 + ni] : make_uint4(0, 0, 0, 0);
+        const uint64_t cw1 = (uint64_t)cd.w << 32;
+        const bool live = desc_live(cw1);
+        const uint32_t cv = desc_sub(cw1, l2_bits);
         uint32_t r = 0, line = 0;
         bool buffered = false;
         if (live) {
@@ -1846,13 +1891,11 @@ k_desc_preagg(const uint4 *__restrict__ data, uint64_t gbase, const uint64_t *__
             __syncthreads();
             // a record past the region's capacity is dropped: the cursor keeps counting and the
             // host reports it (the capacity is the bucket's live descriptors, so none is)
-            const int sub_shift = 64 - l2_bits;
             auto put = [&](uint64_t o, const uint4 &dsc, uint32_t wt) {
                 if (o < ocap) {
                     out[ob + o] = dsc;
                     out_w[ob + o] = wt;
-                    const uint64_t hi = (uint64_t)dsc.w << 32;
-                    out_sub[ob + o] = (uint16_t)(sub_shift < 64 ? hi >> sub_shift : 0);
+                    out_sub[ob + o] = (uint16_t)desc_sub((uint64_t)dsc.w << 32, l2_bits);
                     wacc += wt;
                 }
             };
@@ -1989,7 +2032,7 @@ SkParams sk_params(int k) {
     P.nmax = kDescBases - E + 1;
     P.salt = 0x6d696e696d697aULL;
     P.mini = kMiniOne;
-
+    P.a_epb = P.a_far = 0;
     return P;
 }
 
@@ -2064,7 +2107,15 @@ void node_counter_a(mcaat_ctx *ctx, const mcaat_reads *r, int k, const std::func
     const int fine_bits = pick ? pick(n_occ) : nc_fine_bits(ctx, n_occ);
     P.l2_bits = fine_bits - 8;
     if (pick) P.mini = kMiniShard;  // a rank of a sharded build
-    if (knob_set(ctx, "nc.a_mini")) P.mini = (uint32_t)std::max<int64_t>(8, knob(ctx, "nc.a_mini", 1024)) & ~7u;
+    if (knob_set(ctx, "nc.a_mini"))
+        P.mini = (uint32_t)std::min<int64_t>(kMiniMax, std::max<int64_t>(8, knob(ctx, "nc.a_mini", 1024))) & ~7u;
+    if (knob(ctx, "nc.a_adapt", 1) != 0 && n_items) {
+        // entries per item: the minimizer density over the item's positions, and one for its end
+        const double epi = 2.0 / (P.w + 1) * (double)n_occ / (double)n_items + 1.0;
+        P.a_epb = (uint32_t)std::max<int64_t>(1, std::llround(epi * 64.0));  // 64 items over 256 buckets, in 1/256
+        // a wave with this many batches to come expects to fill a reservation in hand and the next
+        P.a_far = (uint32_t)((512ull * P.mini + (uint64_t)kAWaves * P.a_epb - 1) / ((uint64_t)kAWaves * P.a_epb));
+    }
     bk.l2_bits = P.l2_bits;
     bk.n_occ = n_occ;
     bk.regions.assign(256, {});
@@ -2092,6 +2143,10 @@ void node_counter_a(mcaat_ctx *ctx, const mcaat_reads *r, int k, const std::func
     static const bool prof_a = getenv("MCAAT_PROF_A") && getenv("MCAAT_PROF_A")[0] == '1';
     DevBuf<unsigned long long> dprof(8);
     if (prof_a) HIP_OK(hipMemsetAsync(dprof.p, 0, dprof.bytes(), st));
+    // knob nc.a_stats: the kernel counts its slots (live, inert at reservation switches, inert at
+    // its end), reported as the launch counts of the a_slots_* kernel statistics
+    const bool a_stats = knob(ctx, "nc.a_stats", 0) != 0;
+    DevBuf<unsigned long long> dslots(3);
     for (int attempt = 0;; ++attempt) {
         base[0] = 0;
         for (int b = 0; b < 256; ++b) base[b + 1] = base[b] + cap[b];
@@ -2100,10 +2155,11 @@ void node_counter_a(mcaat_ctx *ctx, const mcaat_reads *r, int k, const std::func
         HIP_OK(hipMemcpyAsync(dcap.p, cap.data(), 8 * 256, hipMemcpyHostToDevice, st));
         HIP_OK(hipMemcpyAsync(dbase.p, base.data(), 8 * 257, hipMemcpyHostToDevice, st));
         HIP_OK(hipMemsetAsync(dcur.p, 0, dcur.bytes(), st));
+        if (a_stats) HIP_OK(hipMemsetAsync(dslots.p, 0, dslots.bytes(), st));
         {
             KernelTimer kt(ctx, "sk_scatter", 0.0);  // bytes added below, once the descriptor count is known
             hipLaunchKernelGGL(sk_kernel(P.w, P.m == 16), dim3((unsigned)a_grid), dim3(kAThreads), 0, st, r->packed.p, src, P, l1.p,
-                               dbase.p, dcap.p, dcur.p, l1s.p, prof_a ? dprof.p : nullptr, nullptr, 0);
+                               dbase.p, dcap.p, dcur.p, l1s.p, prof_a ? dprof.p : nullptr, nullptr, 0, a_stats ? dslots.p : nullptr);
             LAUNCH_OK();
             kt.stop();
         }
@@ -2125,6 +2181,14 @@ void node_counter_a(mcaat_ctx *ctx, const mcaat_reads *r, int k, const std::func
     // algorithmic bytes of the launch: the 2-bit stream read once, a 16-B descriptor and its
     // 2-B sub row written per reserved slot (the tail slots of a reservation are written inert)
     ctx->kstats["sk_scatter"].total_bytes += 0.25 * (double)r->n_bases + 18.0 * (double)n_desc;
+    if (a_stats) {
+        unsigned long long hs[3];
+        d2h(ctx, hs, dslots.p, 24);
+        ctx->kstats["a_slots_reserved"].launches += n_desc;
+        ctx->kstats["a_slots_live"].launches += hs[0];
+        ctx->kstats["a_slots_dead_switch"].launches += hs[1];
+        ctx->kstats["a_slots_dead_end"].launches += hs[2];
+    }
     if (prof_a) {
         unsigned long long hp[8];
         HIP_OK(hipMemcpy(hp, dprof.p, 64, hipMemcpyDeviceToHost));
@@ -2170,7 +2234,8 @@ std::shared_ptr<NcAhead> nc_ahead_begin(mcaat_ctx *ctx, int k, uint64_t n_occ_es
     a->k = k;
     a->P = sk_params(k);
     a->P.l2_bits = nc_fine_bits(ctx, n_occ_est) - 8;
-    if (knob_set(ctx, "nc.a_mini")) a->P.mini = (uint32_t)std::max<int64_t>(8, knob(ctx, "nc.a_mini", 1024)) & ~7u;
+    if (knob_set(ctx, "nc.a_mini"))
+        a->P.mini = (uint32_t)std::min<int64_t>(kMiniMax, std::max<int64_t>(8, knob(ctx, "nc.a_mini", 1024))) & ~7u;
     a->bk = std::make_shared<NcBuckets>();
     a->bk->l2_bits = a->P.l2_bits;
     a->a_grid = (uint64_t)kAPerCu * ctx->n_cu;
@@ -2210,7 +2275,7 @@ void nc_ahead_part(NcAhead &a, const uint64_t *packed, uint64_t n_reads, uint64_
     a.n_occ += n_reads * npos;
     hipLaunchKernelGGL(sk_kernel(a.P.w, a.P.m == 16), dim3((unsigned)a.a_grid), dim3(kAThreads), 0, a.ctx->side, packed,
                        src, a.P, a.bk->data.p, (const uint64_t *)a.dbase.p, (const uint64_t *)a.dcap.p, a.dcur.p,
-                       a.bk->sub.p, nullptr, a.state.p, a.launches ? 2 : 1);
+                       a.bk->sub.p, nullptr, a.state.p, a.launches ? 2 : 1, nullptr);
     LAUNCH_OK();
     ++a.launches;
 }
@@ -2230,7 +2295,7 @@ std::shared_ptr<NcBuckets> nc_ahead_end(NcAhead &a) {
         ItemSrc src{};
         hipLaunchKernelGGL(sk_kernel(a.P.w, a.P.m == 16), dim3((unsigned)a.a_grid), dim3(kAThreads), 0, ctx->side,
                            (const uint64_t *)a.bk->data.p, src, a.P, a.bk->data.p, (const uint64_t *)a.dbase.p,
-                           (const uint64_t *)a.dcap.p, a.dcur.p, a.bk->sub.p, nullptr, a.state.p, a.launches ? 3 : 0);
+                           (const uint64_t *)a.dcap.p, a.dcur.p, a.bk->sub.p, nullptr, a.state.p, a.launches ? 3 : 0, nullptr);
         LAUNCH_OK();
         HIP_OK(hipMemcpyAsync(tot.data(), a.dcur.p, 8 * 256, hipMemcpyDeviceToHost, ctx->side));
     }
@@ -2400,8 +2465,8 @@ void node_counter_preagg(mcaat_ctx *ctx, NcBuckets &bk, int k, NcBuckets &out, u
         if (gn) {
             DevBuf<uint4> fine(gn);
             {
-                KernelTimer kt(ctx, "preagg_partition", 34.0 * (double)gn);
-                hipLaunchKernelGGL(k_l2_scatter<false>, dim3((unsigned)(c1 - c0)), dim3(kBThreads), 0, st, bk.data.p, bk.sub.p,
+                KernelTimer kt(ctx, "preagg_partition", 32.0 * (double)gn);
+                hipLaunchKernelGGL(k_l2_scatter<false>, dim3((unsigned)(c1 - c0)), dim3(kBThreads), 0, st, bk.data.p,
                                    plan.dcs.p + c0, plan.dcl.p + c0, (const uint32_t *)plan.druns.p + c0 * S, bk.l2_bits, E,
                                    fine.p, gbase, (const uint32_t *)nullptr, (uint32_t *)nullptr);
                 LAUNCH_OK();
@@ -2544,10 +2609,10 @@ void node_counter_bc(mcaat_ctx *ctx, NcBuckets &bk, int k, CountResult &out) {
             g.fine.alloc(gn ? gn : 1);
             if (weighted) g.finew.alloc(gn ? gn : 1);
         }
-        auto *kt = new KernelTimer(ctx, "l2_partition", 34.0 * (double)gn, sb);  // sub rows + descriptors read, descriptors written
+        auto *kt = new KernelTimer(ctx, "l2_partition", 32.0 * (double)gn, sb);  // descriptors read, descriptors written
         if (c1 > c0) {
             hipLaunchKernelGGL(weighted ? k_l2_scatter<true> : k_l2_scatter<false>, dim3((unsigned)(c1 - c0)),
-                               dim3(kBThreads), 0, sb, l1.p, l1s.p, dcs.p + c0, dcl.p + c0,
+                               dim3(kBThreads), 0, sb, l1.p, dcs.p + c0, dcl.p + c0,
                                (const uint32_t *)druns.p + c0 * S, P.l2_bits, E, g.fine.p, gbase,
                                (const uint32_t *)bk.wgt.p, g.finew.p);
             LAUNCH_OK();

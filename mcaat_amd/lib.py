@@ -126,6 +126,7 @@ SIGNATURES = {
     "mcaat_comm_unique_id": (C.c_int, [_u8p]),
     "mcaat_comm_schedule_check": (C.c_int, [C.c_int, C.c_uint64, C.c_uint64, _u64p]),
     "mcaat_desc_canonical": (C.c_int, [_u64p, C.c_int, _u64p]),
+    "mcaat_desc_sub": (C.c_int, [C.c_uint64, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_uint32)]),
     "mcaat_comm_init_rccl": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _u8p, C.POINTER(C.c_void_p)]),
     "mcaat_comm_init_shm": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.c_uint64, C.POINTER(C.c_void_p)]),
     "mcaat_comm_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
@@ -186,6 +187,14 @@ def desc_canonical(w0: int, w1: int, E: int) -> Tuple[int, int]:
     dst = (C.c_uint64 * 2)()
     _check(load_library().mcaat_desc_canonical(src, int(E), dst))
     return int(dst[0]), int(dst[1])
+
+
+def desc_sub(w1: int, l2_bits: int) -> Tuple[bool, int]:
+    """(live, fine sub-partition) of a descriptor's second word (mcaat_desc_sub; host only)."""
+    live = C.c_int(0)
+    sub = C.c_uint32(0)
+    _check(load_library().mcaat_desc_sub(int(w1), int(l2_bits), C.byref(live), C.byref(sub)))
+    return bool(live.value), int(sub.value)
 
 
 def preload(device: int = 0) -> None:
