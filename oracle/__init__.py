@@ -1,13 +1,19 @@
-"""TEST INFRASTRUCTURE ONLY — ctypes binding of the CPU restatement (oracle/liboracle.so).
+"""TEST INFRASTRUCTURE ONLY — ctypes binding of the CPU restatement (oracle/liboracle.so), and
+the runner of the reference program's own CycleFinder (oracle/_ref/ref_cf, `make -C oracle ref`).
 
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this.
-Parity status: "parity unpinned" (see oracle/oracle.h and DESIGN.md §Oracle).
+Parity status (oracle/oracle.h): CycleFinder is pinned to the reference program
+at threads = 1, given a graph (tests/test_reference_cycle_finder.py); the SDBG conventions,
+multi-threaded order, cft and rapidfuzz stay unpinned.
 """
 from __future__ import annotations
 
 import ctypes as C
 import os
+import re
+import struct
 import subprocess
+import tempfile
 from typing import List, Sequence, Tuple
 
 import numpy as np
@@ -252,3 +258,132 @@ class OGraph:
             }
         finally:
             L.oracle_cf_free(r)
+
+
+# ---------------------------------------------------------------------------------------------
+# The reference program's CycleFinder (its own cycle_finder.cpp behind the stand-in SDBG of
+# oracle/ref/), run as a child process. Build machine only: `make -C oracle ref` needs the
+# reference tree; the binary it leaves in oracle/_ref/ is never committed.
+REF_BIN = os.path.join(HERE, "_ref", "ref_cf")
+REF_BUILD_COMMAND = "make -C oracle ref"
+
+
+def ref_tree() -> str:
+    return os.environ.get("MCAAT_REFERENCE", "/root/reference")
+
+
+def ref_tree_present() -> bool:
+    return os.path.exists(os.path.join(ref_tree(), "src", "cycle_finder.cpp"))
+
+
+def ref_available() -> bool:
+    """True when the reference runner has been built (oracle/_ref/ref_cf)."""
+    return os.path.exists(REF_BIN)
+
+
+def _write_ref_graph(path: str, keys, mult, k: int, valid) -> None:
+    keys = np.ascontiguousarray(keys, dtype=np.uint64)
+    mult = np.ascontiguousarray(mult, dtype=np.uint16)
+    valid = (np.ones(keys.size, dtype=np.uint8) if valid is None
+             else (np.ascontiguousarray(valid) != 0).astype(np.uint8))
+    assert mult.size == keys.size and valid.size == keys.size
+    with open(path, "wb") as f:
+        f.write(b"MCRG" + struct.pack("<iQ", k, keys.size))
+        f.write(keys.astype("<u8").tobytes())
+        f.write(mult.astype("<u2").tobytes())
+        f.write(valid.tobytes())
+
+
+def _run_ref(args: List[str], timeout: float) -> str:
+    if not ref_available():
+        raise FileNotFoundError(f"{REF_BIN} is missing: run `{REF_BUILD_COMMAND}`")
+    # One OpenMP thread is part of the pin: the reference's CollectTips and
+    # InvalidateMultiplicityOneNodes run `#pragma omp parallel for` with no thread count, and the
+    # tips' order comes from an unordered_set filled under `omp critical`.
+    env = dict(os.environ, OMP_NUM_THREADS="1")
+    p = subprocess.run([REF_BIN] + args, capture_output=True, text=True, timeout=timeout, env=env)
+    if p.returncode != 0:
+        raise RuntimeError(f"ref_cf {args[0]} failed ({p.returncode}): {p.stderr[-2000:]}")
+    return p.stdout
+
+
+_REF_STAT_PATTERNS = [
+    r"gathered tips: (\d+)",
+    r"Pre-filter: invalidated (\d+) node",
+    r"After pruning, tips: \d+, valid edges: (\d+)",
+    r"After pruning, tips: (\d+), valid edges",
+    r"Start nodes found in chunks: (\d+)",
+    r"Cycle enumeration completed: total cycles=(\d+)",
+]
+_REF_CHUNK_LINE = re.compile(r"Chunked start nodes: multiplicity bucket \(log2\)=(-?\d+), nodes=(\d+)")
+
+
+def ref_cycle_finder(keys, mult, k: int, valid=None, threshold_multiplicity=20, low_abundance=True,
+                     cycle_max_length=77, cycle_min_length=27, timeout: float = 300.0) -> dict:
+    """The reference's CycleFinder at threads = 1 on the graph (sorted BOSS keys, mult, initial
+    valid bytes). The dict has OGraph.cycle_finder's shape with `entries` in the iteration order
+    of the reference's `results` map (compare with [ores["entries"][i] for i in ores["map_order"]]),
+    the six stats parsed from the reference's own printed lines, and `valid`, the bytes afterwards.
+    The cluster bound (500) and the step cap (10 000 000) are the reference's, hard-coded."""
+    with tempfile.TemporaryDirectory(prefix="ref_cf_") as d:
+        gpath, rpath = os.path.join(d, "graph.bin"), os.path.join(d, "result.bin")
+        _write_ref_graph(gpath, keys, mult, k, valid)
+        out = _run_ref(["run", gpath, rpath, str(int(threshold_multiplicity)), str(int(bool(low_abundance))),
+                        str(int(cycle_max_length)), str(int(cycle_min_length))], timeout)
+        with open(rpath, "rb") as f:
+            blob = f.read()
+    pos = 0
+
+    def u64(n=1):
+        nonlocal pos
+        a = np.frombuffer(blob, dtype="<u8", count=n, offset=pos)
+        pos += 8 * n
+        return a
+
+    entries = []
+    for _ in range(int(u64()[0])):
+        start, nc = (int(x) for x in u64(2))
+        cycles = []
+        for _ in range(nc):
+            cycles.append([int(x) for x in u64(int(u64()[0]))])
+        entries.append((start, cycles))
+    candidates, buckets, bucket_sizes = [], [], []
+    for _ in range(int(u64()[0])):
+        key = int(u64()[0].astype(np.int64))
+        ids = u64(int(u64()[0]))
+        candidates += [int(x) for x in ids]
+        buckets += [key] * ids.size
+        bucket_sizes.append((key, int(ids.size)))
+    n = int(u64()[0])
+    valid_after = np.frombuffer(blob, dtype=np.uint8, count=n, offset=pos).copy()
+    assert pos + n == len(blob), "result file has trailing bytes"
+    # the constructor's own lines come before the marker the driver prints
+    first, _, second = out.partition("ref_cf: second ChunkStartNodes")
+    stats = []
+    for pat in _REF_STAT_PATTERNS:
+        m = re.search(pat, first)
+        if m is None:
+            raise RuntimeError(f"reference output lacks /{pat}/:\n{first[-2000:]}")
+        stats.append(int(m.group(1)))
+    printed = [(int(a), int(b)) for a, b in _REF_CHUNK_LINE.findall(first)]
+    if printed != bucket_sizes or printed != [(int(a), int(b)) for a, b in _REF_CHUNK_LINE.findall(second)]:
+        raise RuntimeError(f"ChunkStartNodes called again gave {bucket_sizes}, the constructor printed {printed}")
+    return {"entries": entries, "map_order": list(range(len(entries))), "stats": stats,
+            "candidates": candidates, "buckets": buckets, "valid": valid_after, "stdout": out}
+
+
+def ref_neighbors(keys, mult, k: int, valid=None, timeout: float = 120.0) -> Tuple[List[List[int]], List[List[int]]]:
+    """OutgoingEdges / IncomingEdges of every edge from the stand-in SDBG the reference runs on."""
+    with tempfile.TemporaryDirectory(prefix="ref_cf_") as d:
+        gpath, rpath = os.path.join(d, "graph.bin"), os.path.join(d, "nbr.bin")
+        _write_ref_graph(gpath, keys, mult, k, valid)
+        _run_ref(["neighbors", gpath, rpath], timeout)
+        a = np.fromfile(rpath, dtype="<u8")
+    out, inc, pos = [], [], 0
+    for _ in range(len(keys)):
+        for dst in (out, inc):
+            n = int(a[pos])
+            dst.append([int(x) for x in a[pos + 1:pos + 1 + n]])
+            pos += 1 + n
+    assert pos == a.size
+    return out, inc

@@ -2,7 +2,8 @@
  * oracle.cpp — TEST INFRASTRUCTURE ONLY (see oracle.h). CPU restatement of the
  * mcaat hot path. Nothing in the product links this file.
  *
- * Parity status: "parity unpinned" (oracle.h).
+ * Parity status: CycleFinder pinned to the reference program at threads = 1, the SDBG
+ * conventions unpinned (oracle.h).
  *
  * Encoding conventions (DESIGN.md "SDBG conventions", shared with the HIP path
  * only through this written spec, not through code):

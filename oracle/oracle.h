@@ -5,16 +5,25 @@
  * Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may load
  * liboracle.so. The product (libmcaat_gpu.so, mcaat CLI) never links or calls it.
  *
- * PARITY STATUS: "parity unpinned".
- *   - node_counter / sdbg_build are MEGAHIT (absent un-vendored submodule
- *     .gitmodules:10-12 in the reference, no pinned commit); the conventions
- *     restated here are fixed by this repo (DESIGN.md "SDBG conventions").
- *   - cycle_finder.cpp needs MEGAHIT's sdbg/sdbg.h and phmap headers which are
- *     absent from the image; building it would require stand-in headers, which
- *     this project does not write, so the reference is unbuildable here. The
- *     reference ships no golden vectors for the path. The
- *     restatement is therefore validated by analytic known-answer tests
- *     (tests/test_oracle_known_answer.py) and by libstdc++ order probes.
+ * PARITY STATUS
+ *   - CycleFinder: PINNED to the reference program at threads = 1, given a graph.
+ *     `make -C oracle ref` compiles the reference's own src/cycle_finder.cpp, read in
+ *     place from its tree, against two stand-in headers written here (oracle/ref/:
+ *     an SDBG over sorted keys with the conventions of DESIGN.md §2, and phmap's
+ *     flat_hash_set as std::unordered_set) with the driver oracle/ref/ref_cf_main.cpp
+ *     into oracle/_ref/ref_cf (never committed). tests/test_reference_cycle_finder.py
+ *     compares this restatement with live runs of that program (a seeded sweep and
+ *     hand-built graphs at the division of _BackgroundCheck, the length bounds,
+ *     visited and the cluster bound of 500) and the HIP path with its recorded
+ *     results (tests/golden/ref_*.json). The one deviation stays: 64-bit relaxation
+ *     ids where the reference truncates to int (the same below 2^31 edges).
+ *   - UNPINNED: node_counter / sdbg_build are MEGAHIT (absent un-vendored submodule
+ *     .gitmodules:10-12 in the reference, no pinned commit); the edge and neighbour
+ *     order conventions restated here are fixed by this repo and are
+ *     validated by brute-force restatements, analytic known answers and libstdc++
+ *     order probes (tests/test_oracle.py). Also unpinned: the order of results with
+ *     more than one thread. The step cap is bracketed to (9.86 M, 13.47 M) steps by
+ *     the reference; its exact value inside that interval is not.
  */
 #ifndef MCAAT_ORACLE_H
 #define MCAAT_ORACLE_H

@@ -1,7 +1,8 @@
 """Regenerate tests/golden/*.json — oracle outputs on seeded synthetic inputs.
 
-These are regression pins of the CPU restatement (the reference's own hot path cannot
-be built here and ships no vectors). Run: python tests/golden/make_golden.py
+These are regression pins of the CPU restatement: the oracle's own outputs. What the reference
+program's CycleFinder gives is recorded in ref_*.json by make_ref_golden.py.
+Run: python tests/golden/make_golden.py
 """
 import json
 import os

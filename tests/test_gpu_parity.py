@@ -1,7 +1,9 @@
 """GPU parity: every stage of the HIP path against the CPU oracle on the same seeded inputs.
 
 Bar: bit-exact (integer/index work). Calls go through the C ABI (libmcaat_gpu.so).
-Oracle parity status: "parity unpinned"  — the oracle itself is
+Oracle parity status: the oracle's CycleFinder is pinned to the reference program
+at threads = 1 (tests/test_reference_cycle_finder.py, which also runs the HIP path against the
+reference's recorded results); its SDBG conventions (MEGAHIT is absent) stay unpinned and are
 checked by tests/test_oracle.py against brute-force restatements and analytic answers.
 """
 import numpy as np

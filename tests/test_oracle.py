@@ -1,12 +1,14 @@
 """CPU tests of the oracle (test infrastructure) — no GPU.
 
-The oracle is "parity unpinned" (the reference's MEGAHIT-backed path cannot be built
-here and ships no golden vectors). These tests pin it instead to:
+The oracle's CycleFinder is pinned to the reference program itself, at threads = 1, by
+tests/test_reference_cycle_finder.py. Its counting and SDBG conventions stay unpinned (MEGAHIT
+is absent and the reference ships no vectors for them). These tests pin the oracle to:
   * brute-force pure-Python restatements of the SDBG conventions,
   * analytic known answers (a CRISPR array R S1 R ... Sn R yields exactly one cycle per
     spacer whose edges are the (k+1)-mers of the circular string R+Si),
   * a compiled libstdc++ probe of the unordered_set iteration order the GPU emulates,
-  * committed regression fixtures (tests/golden/, made by tests/golden/make_golden.py).
+  * committed regression fixtures (tests/golden/*.json other than ref_*.json, made by
+    tests/golden/make_golden.py: the oracle's own outputs).
 """
 import json
 import os
@@ -229,7 +231,8 @@ def test_dls_requires_cycle_within_limit():
 GOLDEN = os.path.join(HERE, "golden")
 
 
-@pytest.mark.parametrize("name", sorted(f[:-5] for f in os.listdir(GOLDEN) if f.endswith(".json")))
+@pytest.mark.parametrize("name", sorted(f[:-5] for f in os.listdir(GOLDEN)
+                                        if f.endswith(".json") and not f.startswith("ref_")))
 def test_golden_regression(name):
     """Committed oracle outputs (regression pins of the restatement, not reference outputs)."""
     import mcaat_amd as M

@@ -13,7 +13,8 @@
 3. Full C2 / C3 (D > 2^31 at C2): size-independent properties — strictly ascending BOSS
    keys, sum of multiplicities = 2 N_occ, neighbour symmetry and label consistency on a
    sample, every cycle a closed walk of valid edges of length in (min, max].
-Oracle parity status: "parity unpinned" (DESIGN.md §5).
+Oracle parity status: the oracle's CycleFinder is pinned to the reference program
+at threads = 1 by tests/test_reference_cycle_finder.py; its SDBG conventions stay unpinned.
 """
 import numpy as np
 import pytest
