@@ -399,6 +399,12 @@ inline int64_t knob(const mcaat_ctx *ctx, const char *name, int64_t dflt) {
     return it == ctx->knobs.end() ? dflt : it->second;
 }
 
+// the same, held to [lo, hi]
+inline int64_t knob_clamped(const mcaat_ctx *ctx, const char *name, int64_t dflt, int64_t lo, int64_t hi) {
+    const int64_t v = knob(ctx, name, dflt);
+    return v < lo ? lo : v > hi ? hi : v;
+}
+
 inline bool knob_set(const mcaat_ctx *ctx, const char *name) { return ctx->knobs.count(name) != 0; }
 
 inline unsigned grid_for(uint64_t n, unsigned block, unsigned cap = 65535u * 16) {

@@ -31,6 +31,7 @@
 #include <functional>
 #include <memory>
 #include <mutex>
+#include <numeric>
 #include <type_traits>
 
 #include "desc_canon.h"
@@ -107,35 +108,22 @@ __device__ __forceinline__ uint64_t canon_edge(uint64_t lsb, int E) {
 // ballot compaction as {first base, n edges, minimizer hash}; when a segment runs low on
 // room the wave fills in the bases of its entries and the workgroup scatters all segments
 // to the 256 L1 buckets.
-// 4 waves x 1036-entry segments (900 with the bucket bytes, MCAAT_A1HASH=0): ~52 KB of LDS, so
+// 4 waves x 1036-entry segments: ~52 KB of LDS, so
 // three workgroups (12 waves, the VGPR limit at 168 registers) share a CU and one's flush
 // overlaps two others' scans (C3: 87.6 -> 77.8 ms against 2 x 1500)
-#ifndef MCAAT_AREG
-// 1: a lane holds its whole item in registers (fetched an item ahead, its leading s & 31 bases
+// A lane holds its whole item in registers (fetched an item ahead, its leading s & 31 bases
 // shifted out once), so the step loop has no global load, no vmcnt wait and no per-lane 64-bit
-// shift; 0: the window words are loaded a step ahead
-#define MCAAT_AREG 1
-#endif
-#ifndef MCAAT_A1HASH
-// 1: the bucket phase overwrites a pre-entry's minimizer hash with its partition hash, so the
-// bucket (top byte) and the descriptor's hash bits come from the entry: one part_mix per
-// entry and no byte array of buckets; 0: bucket bytes in stage_l1, part_mix twice
-#define MCAAT_A1HASH 1
-#endif
+// shift. The bucket phase overwrites a pre-entry's minimizer hash with its partition hash, so
+// the bucket (top byte) and the descriptor's hash bits come from the entry: one part_mix per
+// entry and no byte array of buckets.
 #ifndef MCAAT_AWAVES
 #define MCAAT_AWAVES 4
 #ifndef MCAAT_ASEG
-// 10 B of LDS per entry without the bucket bytes, 11 with them; 1036 entries are 53,752 B per
-// workgroup, the most that is three workgroups per CU whether the 160 KB are handed out in
-// 512-B or in 1280-B units
-#define MCAAT_ASEG (MCAAT_A1HASH ? 1036 : 900)
+// 10 B of LDS per entry; 1036 entries are 53,752 B per workgroup, the most that is three
+// workgroups per CU whether the 160 KB are handed out in 512-B or in 1280-B units
+#define MCAAT_ASEG 1036
 #endif
 #define MCAAT_APERCU 3
-#endif
-#ifndef MCAAT_HASH
-// minimizer hash: 2 the multiply alone (default since round 5: sk_scatter -1.5 ms at C3, pass C
-// unchanged at C3 and -2 ms at C5), 1 multiply-xorshift, 0 mix32
-#define MCAAT_HASH 2
 #endif
 constexpr int kAWaves = MCAAT_AWAVES;
 constexpr int kAThreads = kAWaves * 64;
@@ -147,11 +135,11 @@ constexpr int kStage = kSeg * kAWaves;  // 8-B pre-entries
 static_assert(kAThreads >= 256, "threads < 256 own one L1 bucket each");
 static_assert(kSeg > 64 * kCk, "a segment must hold a worst-case step");
 static_assert(kStage <= 65536, "perm holds 16-bit stage indices");
-// k_sk_scatter's LDS: stage, perm (and stage_l1), sbase, hist/boff/bcur, rpos/rlim, rleft, wtot, more_flag
-constexpr int kALds = kStage * (8 + 2 + (MCAAT_A1HASH ? 0 : 1)) + kAWaves * 2 * 64 * 8 + 3 * 256 * 4 +
-                      2 * 256 * 8 + 256 * 4 + kAWaves * 4 + 2 * 4;
+// k_sk_scatter's LDS: stage, perm, sbase, hist/boff/bcur, rpos/rlim, rleft, wtot, more_flag
+constexpr int kALds = kStage * (8 + 2) + kAWaves * 2 * 64 * 8 + 3 * 256 * 4 + 2 * 256 * 8 + 256 * 4 +
+                      kAWaves * 4 + 2 * 4;
 static_assert(kALds <= 160 * 1024 / kAPerCu, "kAPerCu workgroups of pass A must fit a CU's LDS");
-constexpr int kItemRegs = 10;  // MCAAT_AREG: 32-bit registers holding an item's bases [0, 160)
+constexpr int kItemRegs = 10;  // 32-bit registers holding an item's bases [0, 160)
 static_assert(kItem + 32 - 1 <= 160, "an item's bases (E <= 32) fit five 64-bit words");
 static_assert(16 * kItemRegs == 160 && kCk == 8, "a step's window starts at a register or half way into one");
 
@@ -165,18 +153,12 @@ struct ItemSrc {
     uint64_t n_items;
 };
 
-// MCAAT_AREG: a wave-uniform value into a scalar register
-#if MCAAT_AREG
+// a wave-uniform value into a scalar register
 __device__ __forceinline__ uint32_t uni(uint32_t x) { return __builtin_amdgcn_readfirstlane(x); }
 __device__ __forceinline__ int uni(int x) { return __builtin_amdgcn_readfirstlane(x); }
 __device__ __forceinline__ uint64_t uni64(uint64_t x) {
     return ((uint64_t)uni((uint32_t)(x >> 32)) << 32) | uni((uint32_t)x);
 }
-#else
-__device__ __forceinline__ uint32_t uni(uint32_t x) { return x; }
-__device__ __forceinline__ int uni(int x) { return x; }
-__device__ __forceinline__ uint64_t uni64(uint64_t x) { return x; }
-#endif
 
 __device__ __forceinline__ void get_item(const ItemSrc &s, int E, uint64_t it, uint64_t &base, int &np) {
     if (s.fixed_len) {
@@ -205,20 +187,10 @@ __device__ __forceinline__ uint64_t rev2_dev(uint64_t x) {
     return ((uint64_t)h << 32) | l;
 }
 
-// 32 bases starting at absolute base B of the packed stream, from its two words
-__device__ __forceinline__ uint64_t win32(uint64_t a, uint64_t b, uint64_t B) {
-    const int sh = 2 * (int)(B & 31);
-    return sh ? (a >> sh) | (b << (64 - sh)) : a;
-}
-
 // hashes of the kCk canonical m-mers starting at the bases 0..kCk-1 of win (m <= 16);
 // FULL: m == 16, so the m-mers need no mask
-#ifndef MCAAT_HTOP
-#define MCAAT_HTOP 1
-#endif
 template <bool FULL>
-__device__ __forceinline__ void hash_step(uint64_t win, int m, uint32_t mmask, uint32_t salt, uint32_t *h) {
-#if MCAAT_HTOP
+__device__ __forceinline__ void hash_step(uint64_t win, int m, uint32_t salt, uint32_t *h) {
     // both m-mers extracted with their bases in the top 2m bits of a 32-bit word (one
     // alignbit each, none at t = 0; the bits below are other bases), so the mask becomes one
     // shift after the min: min(f_top, r_top) >> (32 - 2m) == min(f, r) (equal top fields
@@ -228,48 +200,16 @@ __device__ __forceinline__ void hash_step(uint64_t win, int m, uint32_t mmask, u
     const uint64_t R = rev2_dev(win) ^ ~0ULL;  // complement of base j at bits 62 - 2j
     const uint32_t wl = (uint32_t)Wt, wh = (uint32_t)(Wt >> 32);
     const uint32_t rl = (uint32_t)R, rh = (uint32_t)(R >> 32);
-    (void)mmask;
 #pragma unroll
     for (int t = 0; t < kCk; ++t) {
         const uint32_t f = t ? __builtin_amdgcn_alignbit(wh, wl, 2 * t) : wl;
         const uint32_t r = t ? __builtin_amdgcn_alignbit(rh, rl, 32 - 2 * t) : rh;
         const uint32_t c = FULL ? min(f, r) : min(f, r) >> lo;
-#if MCAAT_HASH == 2
         // a multiply by an odd constant: a bijection whose high bits, which decide the
         // minimizer order, mix every key bit (the buckets and sub-partitions come from a
         // re-hash, so the weak low bits do not matter)
         h[t] = (c ^ salt) * 0x9E3779B1u;
-#elif MCAAT_HASH == 1
-        uint32_t x = (c ^ salt) * 0x9E3779B1u;
-        h[t] = x ^ (x >> 15);
-#else
-        h[t] = mix32(c ^ salt);
-#endif
     }
-#else
-    const uint64_t R = (rev2_dev(win) ^ ~0ULL) >> (2 * (25 - m));  // rc, aligned for t = 7
-    const uint32_t wl = (uint32_t)win, wh = (uint32_t)(win >> 32);
-    const uint32_t rl = (uint32_t)R, rh = (uint32_t)(R >> 32);
-#pragma unroll
-    for (int t = 0; t < kCk; ++t) {
-        uint32_t f = __builtin_amdgcn_alignbit(wh, wl, 2 * t);
-        uint32_t r = __builtin_amdgcn_alignbit(rh, rl, 2 * (kCk - 1 - t));
-        if (!FULL) {
-            f &= mmask;
-            r &= mmask;
-        }
-#if MCAAT_HASH == 2
-        h[t] = (min(f, r) ^ salt) * 0x9E3779B1u;  // A/B: the multiply alone
-#elif MCAAT_HASH == 1
-        // multiply-xorshift: a bijection, and only the minimizer order depends on it (the
-        // buckets and sub-partitions come from a re-hash), so a short one suffices
-        uint32_t x = (min(f, r) ^ salt) * 0x9E3779B1u;
-        h[t] = x ^ (x >> 15);
-#else
-        h[t] = mix32(min(f, r) ^ salt);
-#endif
-    }
-#endif
 }
 
 // minimum over the hashes u .. u+W-1 (u < kCk) of the 3*kCk-entry ring H whose logical
@@ -320,21 +260,10 @@ constexpr uint32_t kAdaptQ = MCAAT_AADAPTQ;
 #ifndef MCAAT_WB
 #define MCAAT_WB 4
 #endif
-#ifndef MCAAT_APF
-#define MCAAT_APF 1
-#endif
-[[maybe_unused]] constexpr int kAPF = MCAAT_APF;  // scan steps of window words in flight (1 or 2)
-constexpr int kWB = MCAAT_WB;
-#ifndef MCAAT_WPIPE
-#define MCAAT_WPIPE 0
-#endif
-#ifndef MCAAT_CLOSEMASK
-#define MCAAT_CLOSEMASK 1
-#endif
-constexpr bool kWPipe = MCAAT_WPIPE != 0;  // write phase: the next batch's loads before this batch's stores  // write batch (entries per thread per round: 3 loads each in flight)
+constexpr int kWB = MCAAT_WB;  // write batch (entries per thread per round: 3 loads each in flight)
 
-// 8-byte pre-entry of a closed super-k-mer: minimizer hash (low 32 bits; MCAAT_A1HASH: the
-// flush's bucket phase puts the partition hash in its place); above it the
+// 8-byte pre-entry of a closed super-k-mer: minimizer hash (low 32 bits; the flush's
+// bucket phase puts the partition hash in its place); above it the
 // close position (7 bits), the first position (7), batch parity (1) and lane (6), all in
 // its item. The item's first base comes from the wave's table of the current and previous
 // batch (sbase), so the pre-entry is half a descriptor and the stage holds 1600 per wave;
@@ -352,9 +281,6 @@ __global__ void __launch_bounds__(kAThreads) k_sk_scatter(const uint64_t *__rest
                                                           unsigned long long *prof, unsigned long long *rstate, int rmode,
                                                           unsigned long long *dstat) {
     __shared__ uint64_t stage[kStage];
-#if !MCAAT_A1HASH
-    __shared__ uint8_t stage_l1[kStage];
-#endif
     __shared__ uint16_t perm[kStage];         // stage entries in bucket order
     __shared__ uint64_t sbase[kAWaves][2][64];  // item first base per (wave, batch parity, lane)
     __shared__ uint32_t hist[256];            // entries per bucket in this flush
@@ -417,9 +343,6 @@ __global__ void __launch_bounds__(kAThreads) k_sk_scatter(const uint64_t *__rest
     if (threadIdx.x == 0) more_flag[0] = more_flag[1] = 0;
     __syncthreads();
     uint64_t *seg = stage + __builtin_amdgcn_readfirstlane(wave * kSeg);  // wave-uniform: a scalar base
-#if !MCAAT_A1HASH
-    uint8_t *seg_l1 = stage_l1 + wave * kSeg;
-#endif
     uint32_t nflush = 0;
 
     // absolute slot; a bucket whose region is exhausted drops the write (its cursor keeps
@@ -434,13 +357,16 @@ __global__ void __launch_bounds__(kAThreads) k_sk_scatter(const uint64_t *__rest
     };
 
     constexpr bool kFull = FULL;  // m == 16: the m-mers need no mask
+    // (mmask here and h_open below are dead since the hash takes the m-mers from the top bits and
+    // an entry its hash from the previous position; they stay because the compiler orders the
+    // kernel's registers differently without them, and this kernel's ISA is the measured one)
     const uint32_t mmask = (uint32_t)mask_bits(2 * P.m);
+    (void)mmask;
     const uint32_t salt32 = (uint32_t)P.salt;
     const int nmax = P.nmax;
 
     // per-lane scan state (wave-uniform: active, c, ph, nck, fill, par, bsf)
     uint32_t H[3 * kCk];  // ring of three 8-hash groups; step c reads groups c, c+1, c+2 (mod 3)
-#if MCAAT_AREG
     // the item's bases from 16 on, 16 per register (bases [0, 16) are only hashed when the item
     // starts); every second step drops a register, so a step's window is always iw[0..2].
     // nraw: the next batch's six words as loaded, (s1, np1) its items; (s2, np2) the batch
@@ -452,15 +378,10 @@ __global__ void __launch_bounds__(kAThreads) k_sk_scatter(const uint64_t *__rest
     int np1 = 0, np2 = 0;
 #pragma unroll
     for (int i = 0; i < kItemRegs - 1; ++i) iw[i] = 0;
-#else
-    uint64_t cw[3], pa = 0, pb = 0;  // the item's first words; the next step's window words
-    uint64_t qa = 0, qb = 0;         // kAPF == 2: the step after next's
-#endif
     uint64_t s = 0;
     int np = 0, c = 0, ph = 0, nck = 0;
     uint32_t prev_hm = 0, h_open = 0, p7 = 0, ihc = 0, fill = 0, par = 1, bsf = 0;
     bool active = false;
-#if MCAAT_AREG
     // items of batch bt (inactive lanes of a tail batch, and batches past the end: base 0, no
     // position)
     auto fetch_item = [&](uint64_t bt, uint64_t &sb, int &n) {
@@ -480,16 +401,6 @@ __global__ void __launch_bounds__(kAThreads) k_sk_scatter(const uint64_t *__rest
             for (int k = 0; k < 3; ++k) nraw[k] = w[k];
         }
     };
-#else
-    auto fetch = [&](uint64_t bt, uint64_t &sb, int &n, uint64_t *w) {
-        const uint64_t item = bt * 64 + lane;
-        sb = 0;
-        n = 0;
-        if (bt < n_batches && item < n_items) get_item(src, P.E, item, sb, n);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) w[k] = packed[(sb >> 5) + k];
-    };
-#endif
 
     // one step: positions 8c .. 8c+7 of the lane's item; the window's bases start at 8c+16.
     // G = c mod 3 names the ring group holding positions 8c.. (compile time, so the ring
@@ -497,7 +408,6 @@ __global__ void __launch_bounds__(kAThreads) k_sk_scatter(const uint64_t *__rest
     auto step = [&](auto Gc) {
         constexpr int G = decltype(Gc)::value;
         c = __builtin_amdgcn_readfirstlane(c);
-#if MCAAT_AREG
         // bases [8c + 16, 8c + 48): an even step's window is iw[0..1], an odd step's lies half
         // a register further (a wave-uniform shift), and after it the registers move down by one
         const uint32_t wsh = (uint32_t)(c & 1) * 16;
@@ -508,22 +418,7 @@ __global__ void __launch_bounds__(kAThreads) k_sk_scatter(const uint64_t *__rest
             for (int i = 0; i + 1 < kItemRegs - 1; ++i) iw[i] = iw[i + 1];
             iw[kItemRegs - 2] = 0;
         }
-#else
-        const int rb = kCk * c + 2 * kCk;
-        const uint64_t win = win32(pa, pb, s + rb);
-        if constexpr (kAPF == 2) {  // the step after next's window words; the next step's were loaded a step ago
-            pa = qa;
-            pb = qb;
-            const u64x2 nx = *(const u64x2 *)(packed + ((s + rb + 2 * kCk) >> 5));
-            qa = nx.a;
-            qb = nx.b;
-        } else {
-            const u64x2 nx = *(const u64x2 *)(packed + ((s + rb + kCk) >> 5));  // next step's window words
-            pa = nx.a;
-            pb = nx.b;
-        }
-#endif
-        hash_step<kFull>(win, P.m, mmask, salt32, H + ((G + 2) % 3) * kCk);
+        hash_step<kFull>(win, P.m, salt32, H + ((G + 2) % 3) * kCk);
         uint32_t hm[kCk];
         window_min<W, G>(H, hm);
         if (c == 0) {
@@ -531,7 +426,6 @@ __global__ void __launch_bounds__(kAThreads) k_sk_scatter(const uint64_t *__rest
             h_open = hm[0];
             p7 = 0;
         }
-#if MCAAT_CLOSEMASK
         // the close test as four compares straight into lane masks (no bool materialised
         // between the ballot and the branch), the closing lanes' region entered on the mask
         // itself; the entry's hash is the previous position's (a super-k-mer's minimizer hash
@@ -557,28 +451,6 @@ __global__ void __launch_bounds__(kAThreads) k_sk_scatter(const uint64_t *__rest
             }
         }
         (void)h_open;
-#else
-#pragma unroll
-        for (int t = 0; t < kCk; ++t) {
-            const int i = kCk * c + t;
-            const uint32_t prv = t ? hm[t - 1] : prev_hm;
-            const bool cl = ((uint32_t)(i - 1) < (uint32_t)np) &
-                            ((i == np) | (hm[t] != prv) | ((int)p7 <= (i - nmax) * 128));
-            const unsigned long long bm = __builtin_amdgcn_ballot_w64(cl);
-            if (bm) {
-                if (cl) {
-                    const uint32_t idx =
-                        __builtin_amdgcn_mbcnt_hi((uint32_t)(bm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bm, fill));
-                    // one 8-B LDS store per close (two 4-B stores at a 2-word stride were 2-way
-                    // bank conflicts for consecutive lanes)
-                    seg[idx] = ((uint64_t)(p7 + ihc + (uint32_t)i) << 32) | h_open;
-                    p7 = (uint32_t)i << kPeP;
-                    h_open = hm[t];
-                }
-                fill += (uint32_t)__popcll(bm);
-            }
-        }
-#endif
         prev_hm = hm[kCk - 1];
     };
 
@@ -595,7 +467,6 @@ __global__ void __launch_bounds__(kAThreads) k_sk_scatter(const uint64_t *__rest
     // a new item hashes its first two groups into the ring groups G, G+1
     auto start_item = [&](auto Gc) {
         constexpr int G = decltype(Gc)::value;
-#if MCAAT_AREG
         // this batch's words were requested when the batch before it started, its items a
         // batch earlier still; the leading s & 31 bases go out here, once (an alignbit by the
         // lane's 2 * (s & 15) and a select on s & 16), so base j of the item is at bit
@@ -635,9 +506,6 @@ __global__ void __launch_bounds__(kAThreads) k_sk_scatter(const uint64_t *__rest
         __builtin_amdgcn_sched_barrier(0);
         fetch_words(batch + bstride, s1);
         fetch_item(batch + 2 * bstride, s2, np2);
-#else
-        fetch(batch, s, np, cw);
-#endif
         par ^= 1u;
         ++bsf;
         sbase[wave][par][lane] = s;
@@ -646,28 +514,11 @@ __global__ void __launch_bounds__(kAThreads) k_sk_scatter(const uint64_t *__rest
 #pragma unroll
         for (int o = 32; o; o >>= 1) mx = max(mx, __shfl_xor(mx, o));
         nck = uni(mx / kCk + 1);  // steps covering positions 0..max np (the last close)
-#if MCAAT_AREG
         // bases [0, 32) and [8, 40)
-        hash_step<kFull>(((uint64_t)iw[0] << 32) | it0, P.m, mmask, salt32, H + G * kCk);
+        hash_step<kFull>(((uint64_t)iw[0] << 32) | it0, P.m, salt32, H + G * kCk);
         hash_step<kFull>(((uint64_t)__builtin_amdgcn_alignbit(iw[1], iw[0], 16) << 32) |
                              __builtin_amdgcn_alignbit(iw[0], it0, 16),
-                         P.m, mmask, salt32, H + ((G + 1) % 3) * kCk);
-#else
-        {
-            const u64x2 nx = *(const u64x2 *)(packed + ((s + 2 * kCk) >> 5));
-            pa = nx.a;
-            pb = nx.b;
-        }
-        if constexpr (kAPF == 2) {
-            const u64x2 nx = *(const u64x2 *)(packed + ((s + 3 * kCk) >> 5));
-            qa = nx.a;
-            qb = nx.b;
-        }
-        const int o8 = (int)(s & 31) + kCk;
-        hash_step<kFull>(win32(cw[0], cw[1], s), P.m, mmask, salt32, H + G * kCk);
-        hash_step<kFull>(o8 >= 32 ? win32(cw[1], cw[2], s + kCk) : win32(cw[0], cw[1], s + kCk), P.m, mmask,
-                         salt32, H + ((G + 1) % 3) * kCk);
-#endif
+                         P.m, salt32, H + ((G + 1) % 3) * kCk);
         c = 0;
         active = true;
     };
@@ -698,11 +549,9 @@ __global__ void __launch_bounds__(kAThreads) k_sk_scatter(const uint64_t *__rest
         return true;
     };
 
-#if MCAAT_AREG
     fetch_item(batch, s1, np1);
     fetch_words(batch, s1);
     fetch_item(batch + bstride, s2, np2);
-#endif
     for (;;) {
         // the scan is unrolled over the three ring phases; a flush may interrupt it at any
         // phase, so the ring is rotated back to phase 0 first (once per flush)
@@ -727,8 +576,7 @@ __global__ void __launch_bounds__(kAThreads) k_sk_scatter(const uint64_t *__rest
         }
         tick(0);
         // bucket of each entry: the minimum hash is biased towards 0, so buckets come from
-        // a re-hash of it (a bijection)
-#if MCAAT_A1HASH
+        // a re-hash of it (a bijection);
         // the partition hash takes the minimizer hash's place in the entry (nothing after this
         // reads the latter): the permutation pass and the write phase take the bucket and the
         // descriptor's hash bits from it
@@ -738,13 +586,6 @@ __global__ void __launch_bounds__(kAThreads) k_sk_scatter(const uint64_t *__rest
             *lo = pm;
             atomicAdd(&hist[pm >> 24], 1u);
         }
-#else
-        for (uint32_t e = lane; e < fill; e += 64) {
-            const uint32_t l1 = part_mix((uint32_t)seg[e]) >> 24;
-            seg_l1[e] = (uint8_t)l1;
-            atomicAdd(&hist[l1], 1u);
-        }
-#endif
         tick(1);
         if (lane == 0) wtot[wave] = fill;
         if (lane == 0 && (active || batch < n_batches)) more_flag[nflush & 1] = 1;
@@ -790,11 +631,7 @@ __global__ void __launch_bounds__(kAThreads) k_sk_scatter(const uint64_t *__rest
         if (tb < 256) hist[tb] = 0;
         tick(3);
         for (uint32_t e = lane; e < fill; e += 64) {
-#if MCAAT_A1HASH
             const int b = (int)(*(const uint32_t *)(seg + e) >> 24);
-#else
-            const int b = seg_l1[e];
-#endif
             perm[boff[b] + atomicAdd(&bcur[b], 1u)] = (uint16_t)(wave * kSeg + e);
         }
         lds_barrier();  // C: perm ready
@@ -805,80 +642,54 @@ __global__ void __launch_bounds__(kAThreads) k_sk_scatter(const uint64_t *__rest
         for (int w = 0; w < kAWaves; ++w) total += wtot[w];
         if (dstat && threadIdx.x == 0 && total) atomicAdd(&dstat[0], (unsigned long long)total);
         // a batch of kWB entries per thread: first its stage reads and base loads, then the
-        // descriptors; with kWPipe the next batch's loads are issued before this batch's
-        // descriptors are built (two batches of registers, slots fixed at compile time)
-        uint64_t q[2][kWB], B0[2][kWB], x[2][kWB][3];
-        auto load_batch = [&](auto Sc, uint32_t j0) {
-            constexpr int S = decltype(Sc)::value;
+        // descriptors
+        uint64_t q[kWB], B0[kWB], x[kWB][3];
+        auto load_batch = [&](uint32_t j0) {
 #pragma unroll
             for (int k = 0; k < kWB; ++k) {
                 const uint32_t j = j0 + k * kAThreads;
-                q[S][k] = 0;
-                B0[S][k] = 0;
+                q[k] = 0;
+                B0[k] = 0;
                 if (j < total) {
                     const uint32_t i = perm[j];
-                    q[S][k] = stage[i];
-                    const uint32_t hi = (uint32_t)(q[S][k] >> 32);
+                    q[k] = stage[i];
+                    const uint32_t hi = (uint32_t)(q[k] >> 32);
                     const uint32_t ln = (hi >> kPeLane) & 63, pr = (hi >> kPePar) & 1;
-                    B0[S][k] = sbase[i / kSeg][pr][ln] + ((hi >> kPeP) & 127);
+                    B0[k] = sbase[i / kSeg][pr][ln] + ((hi >> kPeP) & 127);
                 }
                 // the first two words in one 16-B load; the third only when the bases reach
                 // it (these loads are uncoalesced, so the vector L1 pays per lane and line)
-                const int L = (int)(((uint32_t)(q[S][k] >> 32) & 127) - (((uint32_t)(q[S][k] >> 32) >> kPeP) & 127)) + P.E - 1;
-                const u64x2 x01 = *(const u64x2 *)(packed + (B0[S][k] >> 5));
-                x[S][k][0] = x01.a;
-                x[S][k][1] = x01.b;
-                x[S][k][2] = j < total && 2 * (int)(B0[S][k] & 31) + 2 * L > 128 ? packed[(B0[S][k] >> 5) + 2] : 0;
+                const int L = (int)(((uint32_t)(q[k] >> 32) & 127) - (((uint32_t)(q[k] >> 32) >> kPeP) & 127)) + P.E - 1;
+                const u64x2 x01 = *(const u64x2 *)(packed + (B0[k] >> 5));
+                x[k][0] = x01.a;
+                x[k][1] = x01.b;
+                x[k][2] = j < total && 2 * (int)(B0[k] & 31) + 2 * L > 128 ? packed[(B0[k] >> 5) + 2] : 0;
             }
         };
-        auto store_batch = [&](auto Sc, uint32_t j0) {
-            constexpr int S = decltype(Sc)::value;
+        auto store_batch = [&](uint32_t j0) {
 #pragma unroll
             for (int k = 0; k < kWB; ++k) {
                 const uint32_t j = j0 + k * kAThreads;
                 if (j >= total) continue;
-#if MCAAT_A1HASH
-                const uint32_t h = (uint32_t)q[S][k];  // the partition hash (bucket phase)
+                const uint32_t h = (uint32_t)q[k];  // the partition hash (bucket phase)
                 const int b = (int)(h >> 24);
-#else
-                const uint32_t i = perm[j];
-                const int b = stage_l1[i];
-#endif
-                const uint32_t hi = (uint32_t)(q[S][k] >> 32);
+                const uint32_t hi = (uint32_t)(q[k] >> 32);
                 const uint32_t n = (hi & 127) - ((hi >> kPeP) & 127);
-                const int sh = 2 * (int)(B0[S][k] & 31);
+                const int sh = 2 * (int)(B0[k] & 31);
                 // bases past the last edge are zeroed, so every copy of a super-k-mer is the
                 // same 128-bit descriptor whatever follows it in its read
                 const int L = (int)n + P.E - 1;
-                const uint64_t w0 = (sh ? (x[S][k][0] >> sh) | (x[S][k][1] << (64 - sh)) : x[S][k][0]) & mask_bits(2 * L);
-                uint64_t w1 = (sh ? (x[S][k][1] >> sh) | (x[S][k][2] << (64 - sh)) : x[S][k][1]) &
+                const uint64_t w0 = (sh ? (x[k][0] >> sh) | (x[k][1] << (64 - sh)) : x[k][0]) & mask_bits(2 * L);
+                uint64_t w1 = (sh ? (x[k][1] >> sh) | (x[k][2] << (64 - sh)) : x[k][1]) &
                               mask_bits(L > 32 ? 2 * (L - 32) : 0);
-#if !MCAAT_A1HASH
-                const uint32_t h = part_mix((uint32_t)q[S][k]);
-#endif
                 w1 |= ((uint64_t)n << kNShift) | ((uint64_t)((h >> (24 - kHBits)) & ((1u << kHBits) - 1)) << kHShift);
                 put(b, rpos[b] + (j - boff[b]),
                     make_uint4((uint32_t)w0, (uint32_t)(w0 >> 32), (uint32_t)w1, (uint32_t)(w1 >> 32)));
             }
         };
-        constexpr uint32_t kStep = kWB * kAThreads;
-        using S0 = std::integral_constant<int, 0>;
-        using S1 = std::integral_constant<int, 1>;
-        if constexpr (kWPipe) {
-            uint32_t j0 = threadIdx.x;
-            if (j0 < total) load_batch(S0(), j0);
-            for (; j0 < total; j0 += 2 * kStep) {
-                if (j0 + kStep < total) load_batch(S1(), j0 + kStep);
-                store_batch(S0(), j0);
-                if (j0 + kStep >= total) break;
-                if (j0 + 2 * kStep < total) load_batch(S0(), j0 + 2 * kStep);
-                store_batch(S1(), j0 + kStep);
-            }
-        } else {
-            for (uint32_t j0 = threadIdx.x; j0 < total; j0 += kStep) {
-                load_batch(S0(), j0);
-                store_batch(S0(), j0);
-            }
+        for (uint32_t j0 = threadIdx.x; j0 < total; j0 += kWB * kAThreads) {
+            load_batch(j0);
+            store_batch(j0);
         }
         if (tb < 256) bcur[tb] = 0;
         fill = 0;
@@ -1038,10 +849,6 @@ constexpr int kMaxSub = 2048;   // l2_bits <= 11: 128 KB of line buffers
 #define MCAAT_BPF 2
 #endif
 constexpr int kBPF = MCAAT_BPF;  // rounds of descriptor loads in flight
-#ifndef MCAAT_BCOOP
-#define MCAAT_BCOOP 1
-#endif
-constexpr bool kCoopFlush = MCAAT_BCOOP != 0;  // completed lines written by the whole wave
 
 // WEIGHTED (a sharded build's owner after a sender-side collapse, dist.preagg): each descriptor's
 // 32-bit multiplicity goes to the same fine-partition slot of out_w, written directly (the line
@@ -1105,41 +912,31 @@ __global__ void __launch_bounds__(kBThreads) k_l2_scatter(const uint4 *__restric
         }
         lds_barrier();
         uint32_t nline = 0;
-        if (kCoopFlush) {
-            // the lines completed this round leave the wave kLG lanes per line, each lane one
-            // 16-B piece: one store instruction writes 64/kLG whole lines (one lane per line
-            // with kLG stores before), and the LDS reads are kLG-lane contiguous runs
-            const bool done = live && buffered && (r & (kLG - 1)) == kLG - 1;
-            const unsigned long long dm = __ballot(done);
-            const uint32_t lane = threadIdx.x & 63;
-            const uint64_t dst = done ? ((uint64_t)lb[cv] + line) * kLG - gbase : 0;
-            const uint32_t src = done ? cv * kLG : 0;
-            const int nd = __popcll(dm);
-            for (int b0 = 0; b0 < nd; b0 += 64 / kLG) {
-                const int j = b0 + (int)(lane / kLG);  // the line this lane helps write
-                // lane holding the j-th set bit of dm (binary search on prefix popcounts)
-                int pos = 0;
-                if (j < nd) {
+        // the lines completed this round leave the wave kLG lanes per line, each lane one
+        // 16-B piece: one store instruction writes 64/kLG whole lines (one lane per line
+        // with kLG stores before), and the LDS reads are kLG-lane contiguous runs
+        const bool done = live && buffered && (r & (kLG - 1)) == kLG - 1;
+        const unsigned long long dm = __ballot(done);
+        const uint32_t lane = threadIdx.x & 63;
+        const uint64_t dst = done ? ((uint64_t)lb[cv] + line) * kLG - gbase : 0;
+        const uint32_t src = done ? cv * kLG : 0;
+        const int nd = __popcll(dm);
+        for (int b0 = 0; b0 < nd; b0 += 64 / kLG) {
+            const int j = b0 + (int)(lane / kLG);  // the line this lane helps write
+            // lane holding the j-th set bit of dm (binary search on prefix popcounts)
+            int pos = 0;
+            if (j < nd) {
 #pragma unroll
-                    for (int step = 32; step; step >>= 1) {
-                        const unsigned long long below = dm & ((pos + step >= 64) ? ~0ull : ((1ull << (pos + step)) - 1));
-                        if (__popcll(below) <= j) pos += step;
-                    }
+                for (int step = 32; step; step >>= 1) {
+                    const unsigned long long below = dm & ((pos + step >= 64) ? ~0ull : ((1ull << (pos + step)) - 1));
+                    if (__popcll(below) <= j) pos += step;
                 }
-                const uint64_t d = __shfl(dst, pos);
-                const uint32_t sidx = __shfl(src, pos);
-                if (j < nd) out[d + (lane & (kLG - 1))] = buf[sidx + (lane & (kLG - 1))];
             }
-            if (live) {
-                nline = lc[cv] / kLG;
-                bl[cv] = nline;  // every writer stores the same value
-            }
-        } else if (live) {
-            if (buffered && (r & (kLG - 1)) == kLG - 1) {
-                uint4 *o = out + (((uint64_t)lb[cv] + line) * kLG - gbase);
-#pragma unroll
-                for (int z = 0; z < kLG; ++z) o[z] = buf[cv * kLG + z];
-            }
+            const uint64_t d = __shfl(dst, pos);
+            const uint32_t sidx = __shfl(src, pos);
+            if (j < nd) out[d + (lane & (kLG - 1))] = buf[sidx + (lane & (kLG - 1))];
+        }
+        if (live) {
             nline = lc[cv] / kLG;
             bl[cv] = nline;  // every writer stores the same value
         }
@@ -1181,10 +978,6 @@ constexpr int kDProbe = 128;                               // probe bound of the
 #define MCAAT_CB 1
 #endif
 constexpr int kCB = MCAAT_CB;                              // descriptor loads in flight per thread
-#ifndef MCAAT_CPF
-#define MCAAT_CPF 1
-#endif
-constexpr bool kCPF = MCAAT_CPF != 0;                      // next round's loads issued before the probes
 #ifndef MCAAT_CPERCU
 #define MCAAT_CPERCU 2
 #endif
@@ -1195,25 +988,6 @@ constexpr int kCPerCu = MCAAT_CPERCU;                      // resident workgroup
 constexpr uint32_t kSplitLg = MCAAT_CSPLIT;                // log2 classes of an overflowing partition (<= 3 spare hash bits)
 static_assert(kSplitLg <= 3, "the sub-partition takes the top 11 of the 14 stored hash bits");
 constexpr uint32_t kSplitMax = 3;                          // spare hash bits: deepest class split
-#ifndef MCAAT_CRING
-#define MCAAT_CRING 0
-#endif
-// collapse rounds in flight in an LDS-DMA ring (0: the register prefetch below). Measured and
-// rejected (round 3, C3): a 2-round ring, 74.8 KB of LDS per workgroup, took pass C 56.4 -> 62.6 ms
-constexpr int kCRing = MCAAT_CRING;
-// one 16-B LDS-DMA per lane: lds is the wave-uniform base, lane i lands at lds + 16 i
-// (inline asm: the compiler's own wait bookkeeping would otherwise drain every DMA before the
-// next LDS access, vmcnt(0); the callers count their DMAs with wait_vm0 / wait_vm1)
-__device__ __forceinline__ void dma16(const uint4 *src, uint4 *lds) {
-    const uint32_t dst = __builtin_amdgcn_readfirstlane(
-        (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void *)lds);
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(src), "s"(dst) : "memory");
-}
-__device__ __forceinline__ void wait_vm0() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-__device__ __forceinline__ void wait_vm1() { asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); }
-__device__ __forceinline__ void wait_lgkm0() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
 // overflow-list entry: partition (24 bits), class (4), log2 class count (4)
 __device__ __forceinline__ uint32_t ovf_part(uint32_t e) { return e & 0xFFFFFFu; }
@@ -1276,12 +1050,8 @@ __global__ void __launch_bounds__(kCThreads, PERCU * kCThreads / 256) k_lds_coun
     // between the phases each thread keeps its two descriptor slots in registers. 48 KB per
     // workgroup, so two 1024-thread workgroups share a CU and one's loads overlap the other's
     // LDS work.
-    // With kCRing > 0 the collapse streams the partition through a ring of kCRing rounds of
-    // descriptors placed after the descriptor table, filled by LDS-DMA (global_load_lds): the
-    // loads of the next kCRing rounds are in flight without holding registers.
-    constexpr int kEdgeBytes = kCap * 12, kDescBytes = kDCap * 20, kRingBytes = kCRing * kCThreads * 16;
-    constexpr int kCollBytes = kDescBytes + kRingBytes;
-    __shared__ __attribute__((aligned(16))) unsigned char region[kEdgeBytes > kCollBytes ? kEdgeBytes : kCollBytes];
+    constexpr int kEdgeBytes = kCap * 12, kDescBytes = kDCap * 20;
+    __shared__ __attribute__((aligned(16))) unsigned char region[kEdgeBytes > kDescBytes ? kEdgeBytes : kDescBytes];
     unsigned long long *const keys = (unsigned long long *)region;
     uint32_t *const cnt = (uint32_t *)(keys + kCap);
     unsigned long long *const dk0 = (unsigned long long *)region, *const dk1 = dk0 + kDCap;
@@ -1405,51 +1175,15 @@ __global__ void __launch_bounds__(kCThreads, PERCU * kCThreads / 256) k_lds_coun
             dovf = 1;
             if (PROF) atomicAdd(&prof[5], 1ull);
         };
-        if constexpr (kCRing > 0) {
-            // LDS-DMA ring: wave w's 64 lanes land round r's descriptors d0 + 64w .. in slot
-            // r % kCRing (one 1-KB global_load_lds per wave); a lane reads back only its own
-            // entry, so no barrier orders the waves, and each wave counts its own DMAs (vmcnt)
-            uint4 *const ring = (uint4 *)(region + kDescBytes);
-            auto issue = [&](uint64_t d0, int slot) {
-                const uint64_t d = d0 + threadIdx.x;
-                const uint4 *src = data + (d < end ? d : beg);  // in bounds; masked when read
-                dma16(src, ring + slot * kCThreads + wave * 64);
-            };
-#pragma unroll
-            for (int r = 0; r < kCRing; ++r)
-                if (beg + (uint64_t)r * kCThreads < end) issue(beg + (uint64_t)r * kCThreads, r);
-            int slot = 0;
-            for (uint64_t d0 = beg; d0 < end; d0 += kCThreads) {
-                if (__hip_atomic_load(&dovf, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) break;
-                // DMAs issued after this round's (uniform): rounds d0+1 .. min(d0+kCRing-1, last)
-                const uint64_t left = (end - d0 - 1) / kCThreads;  // rounds after this one
-                if (left >= 1 && kCRing >= 2) wait_vm1(); else wait_vm0();
-                const uint4 cq = ring[slot * kCThreads + threadIdx.x];
-                const uint64_t d = d0 + threadIdx.x;
-                if (left >= (uint64_t)kCRing) {
-                    wait_lgkm0();  // the read has landed before the DMA may overwrite the slot
-                    issue(d0 + (uint64_t)kCRing * kCThreads, slot);
-                }
-                if (d < end) {
-                    uint32_t wt = 1u;
-                    if constexpr (WEIGHTED) wt = wgt[d];
-                    collapse((uint64_t)cq.x | ((uint64_t)cq.y << 32), (uint64_t)cq.z | ((uint64_t)cq.w << 32), wt);
-                }
-                slot = slot + 1 == kCRing ? 0 : slot + 1;
-            }
-            wait_vm0();  // no DMA may land in the region once it becomes the edge table
-        } else {
         // kCB descriptors per thread per round: their loads are all in flight together, and
-        // with kCPF the next round's are issued before this round's probes
+        // the next round's are issued before this round's probes
         uint4 q[kCB];
         uint32_t qw[kCB];  // WEIGHTED: the slots' multiplicities, loaded beside the descriptors
-        if (kCPF) {
 #pragma unroll
-            for (int k = 0; k < kCB; ++k) {
-                const uint64_t d = beg + threadIdx.x + (uint64_t)k * kCThreads;
-                q[k] = d < end ? data[d] : make_uint4(0, 0, 0, 0);
-                if constexpr (WEIGHTED) qw[k] = d < end ? wgt[d] : 0u;
-            }
+        for (int k = 0; k < kCB; ++k) {
+            const uint64_t d = beg + threadIdx.x + (uint64_t)k * kCThreads;
+            q[k] = d < end ? data[d] : make_uint4(0, 0, 0, 0);
+            if constexpr (WEIGHTED) qw[k] = d < end ? wgt[d] : 0u;
         }
         for (uint64_t d0 = beg + threadIdx.x; d0 < end; d0 += (uint64_t)kCThreads * kCB) {
             if (__hip_atomic_load(&dovf, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) break;
@@ -1458,24 +1192,17 @@ __global__ void __launch_bounds__(kCThreads, PERCU * kCThreads / 256) k_lds_coun
 #pragma unroll
             for (int k = 0; k < kCB; ++k) {
                 cw[k] = 1u;
-                if (kCPF) {
-                    cq[k] = q[k];
-                    if constexpr (WEIGHTED) cw[k] = qw[k];
-                    const uint64_t d = d0 + (uint64_t)(k + kCB) * kCThreads;
-                    q[k] = d < end ? data[d] : make_uint4(0, 0, 0, 0);
-                    if constexpr (WEIGHTED) qw[k] = d < end ? wgt[d] : 0u;
-                } else {
-                    const uint64_t d = d0 + (uint64_t)k * kCThreads;
-                    cq[k] = d < end ? data[d] : make_uint4(0, 0, 0, 0);
-                    if constexpr (WEIGHTED) cw[k] = d < end ? wgt[d] : 0u;
-                }
+                cq[k] = q[k];
+                if constexpr (WEIGHTED) cw[k] = qw[k];
+                const uint64_t d = d0 + (uint64_t)(k + kCB) * kCThreads;
+                q[k] = d < end ? data[d] : make_uint4(0, 0, 0, 0);
+                if constexpr (WEIGHTED) qw[k] = d < end ? wgt[d] : 0u;
             }
 #pragma unroll
             for (int k = 0; k < kCB; ++k)
                 if (d0 + (uint64_t)k * kCThreads < end)
                     collapse((uint64_t)cq[k].x | ((uint64_t)cq[k].y << 32), (uint64_t)cq[k].z | ((uint64_t)cq[k].w << 32),
                              cw[k]);
-        }
         }
         __syncthreads();
         tick(1);
@@ -1981,13 +1708,47 @@ void exclusive_scan(mcaat_ctx *ctx, const T *in, T *out, uint64_t n) {
     HIP_OK(hipcub::DeviceScan::ExclusiveSum(t.p, tmp, in, out, (size_t)n, ctx->stream));
 }
 
+// L1 bucket capacities: the expected descriptors (density 2/(w+1) per edge + one per item) with
+// headroom, + one partially used and one prefetched reservation per (workgroup, bucket)
+std::vector<uint64_t> l1_caps(mcaat_ctx *ctx, const SkParams &P, uint64_t a_grid, uint64_t n_occ, uint64_t n_items,
+                              double headroom) {
+    const double dens = 2.0 / (P.w + 1);
+    const uint64_t est = (uint64_t)(headroom * (dens * (double)n_occ + (double)n_items)) + 4096;
+    uint64_t slots = est / 256 + 2 * a_grid * P.mini;
+    if (const int64_t fixed = knob(ctx, "nc.l1_slots", 0)) slots = (uint64_t)fixed;  // test knob: undersize -> resize and re-run
+    return std::vector<uint64_t>(256, (slots + 7) & ~7ull);  // 16-B aligned sub rows
+}
+
+// the buffers of a bucket set without descriptors (the later passes take their addresses)
+void alloc_empty(NcBuckets &bk, bool weighted) {
+    bk.data.alloc(1);
+    bk.sub.alloc(8);
+    if (weighted) bk.wgt.alloc(8);
+}
+
+// pass A's result from its cursors (tot: whole reservations per bucket); returns the slots reserved
+uint64_t set_regions(NcBuckets &bk, const std::vector<uint64_t> &base, const std::vector<unsigned long long> &tot) {
+    uint64_t n_desc = 0;
+    bk.base = base;
+    bk.regions.assign(256, {});
+    for (int b = 0; b < 256; ++b) {
+        n_desc += tot[b];
+        if (tot[b]) bk.regions[b].push_back({base[b], tot[b]});
+    }
+    return n_desc;
+}
+
+bool verbose_on() {
+    static const bool on = getenv("MCAAT_VERBOSE") && getenv("MCAAT_VERBOSE")[0] == '1';
+    return on;
+}
+
 }  // namespace
 
 // MCAAT_VERBOSE=1: host wall-clock marks of the sub-stages on stderr (stream-synchronised)
 void verbose_mark(mcaat_ctx *ctx, const char *what) {
-    static const bool on = getenv("MCAAT_VERBOSE") && getenv("MCAAT_VERBOSE")[0] == '1';
     static double last = 0;
-    if (!on) return;
+    if (!verbose_on()) return;
     timespec ts;
     clock_gettime(CLOCK_MONOTONIC, &ts);
     const double pre = ts.tv_sec * 1e3 + ts.tv_nsec / 1e6;
@@ -2009,8 +1770,9 @@ int nc_fine_bits(mcaat_ctx *ctx, uint64_t n_occ) {
     return std::max(8, std::min(19, fine_bits));  // l2_bits <= 11: k_l2_scatter's line buffers
 }
 
-// pass A's minimizer parameters for k (every pass A launch for k uses the same)
-SkParams sk_params(int k) {
+// pass A's minimizer parameters for k (every pass A launch for k uses the same); shard: a rank of
+// a sharded build
+SkParams sk_params(mcaat_ctx *ctx, int k, bool shard) {
     const int E = k + 1;
     SkParams P;
     P.E = E;
@@ -2031,7 +1793,8 @@ SkParams sk_params(int k) {
     if (P.w > 16) throw Error(MCAAT_E_INVALID, "node_counter: minimizer window above 16");
     P.nmax = kDescBases - E + 1;
     P.salt = 0x6d696e696d697aULL;
-    P.mini = kMiniOne;
+    P.mini = shard ? kMiniShard : kMiniOne;
+    if (knob_set(ctx, "nc.a_mini")) P.mini = (uint32_t)knob_clamped(ctx, "nc.a_mini", 1024, 8, kMiniMax) & ~7u;
     P.a_epb = P.a_far = 0;
     return P;
 }
@@ -2057,7 +1820,7 @@ void node_counter_a(mcaat_ctx *ctx, const mcaat_reads *r, int k, const std::func
     verbose_mark(ctx, "node_counter.begin");
     const int E = k + 1;
     hipStream_t st = ctx->stream;
-    SkParams P = sk_params(k);
+    SkParams P = sk_params(ctx, k, pick != nullptr);
     // work items (<= kItem edge positions each)
     ItemSrc src{};
     src.offsets = r->offsets.p;
@@ -2106,9 +1869,6 @@ void node_counter_a(mcaat_ctx *ctx, const mcaat_reads *r, int k, const std::func
     }
     const int fine_bits = pick ? pick(n_occ) : nc_fine_bits(ctx, n_occ);
     P.l2_bits = fine_bits - 8;
-    if (pick) P.mini = kMiniShard;  // a rank of a sharded build
-    if (knob_set(ctx, "nc.a_mini"))
-        P.mini = (uint32_t)std::min<int64_t>(kMiniMax, std::max<int64_t>(8, knob(ctx, "nc.a_mini", 1024))) & ~7u;
     if (knob(ctx, "nc.a_adapt", 1) != 0 && n_items) {
         // entries per item: the minimizer density over the item's positions, and one for its end
         const double epi = 2.0 / (P.w + 1) * (double)n_occ / (double)n_items + 1.0;
@@ -2120,21 +1880,13 @@ void node_counter_a(mcaat_ctx *ctx, const mcaat_reads *r, int k, const std::func
     bk.n_occ = n_occ;
     bk.regions.assign(256, {});
     if (n_occ == 0) {
-        bk.data.alloc(1);
-        bk.sub.alloc(8);
+        alloc_empty(bk, false);
         return;
     }
 
     // ---- A ----
-    // expected descriptors: density 2/(w+1) per edge + one per item, with headroom
-    const double dens = 2.0 / (P.w + 1);
-    uint64_t est = (uint64_t)(1.08 * (dens * (double)n_occ + (double)n_items)) + 4096;
-    std::vector<uint64_t> cap(256), base(257);
-    // + one partially used reservation per (workgroup, bucket)
     const uint64_t a_grid = (uint64_t)kAPerCu * ctx->n_cu;
-    for (int b = 0; b < 256; ++b) cap[b] = (est / 256 + 2 * a_grid * P.mini + 7) & ~7ull;  // 16-B aligned sub rows
-    if (const int64_t fixed = knob(ctx, "nc.l1_slots", 0))  // test knob: undersize -> resize and re-run
-        for (int b = 0; b < 256; ++b) cap[b] = ((uint64_t)fixed + 7) & ~7ull;
+    std::vector<uint64_t> cap = l1_caps(ctx, P, a_grid, n_occ, n_items, 1.08), base(257, 0);
     DevBuf<uint64_t> dcap(256), dbase(257);
     DevBuf<unsigned long long> dcur(256);
     DevBuf<uint4> &l1 = bk.data;
@@ -2148,8 +1900,7 @@ void node_counter_a(mcaat_ctx *ctx, const mcaat_reads *r, int k, const std::func
     const bool a_stats = knob(ctx, "nc.a_stats", 0) != 0;
     DevBuf<unsigned long long> dslots(3);
     for (int attempt = 0;; ++attempt) {
-        base[0] = 0;
-        for (int b = 0; b < 256; ++b) base[b + 1] = base[b] + cap[b];
+        std::partial_sum(cap.begin(), cap.end(), base.begin() + 1);
         l1.alloc(base[256]);
         l1s.alloc(base[256]);
         HIP_OK(hipMemcpyAsync(dcap.p, cap.data(), 8 * 256, hipMemcpyHostToDevice, st));
@@ -2172,12 +1923,7 @@ void node_counter_a(mcaat_ctx *ctx, const mcaat_reads *r, int k, const std::func
         if (attempt > 0) throw Error(MCAAT_E_CAPACITY, "node_counter: L1 bucket sizing failed");
         for (int b = 0; b < 256; ++b) cap[b] = (tot[b] + 8) & ~7ull;  // exact on the second run (cursors count every grab)
     }
-    uint64_t n_desc = 0;
-    bk.base = base;
-    for (int b = 0; b < 256; ++b) {
-        n_desc += tot[b];
-        if (tot[b]) bk.regions[b].push_back({base[b], tot[b]});  // tot: whole reservations
-    }
+    const uint64_t n_desc = set_regions(bk, base, tot);
     // algorithmic bytes of the launch: the 2-bit stream read once, a 16-B descriptor and its
     // 2-B sub row written per reserved slot (the tail slots of a reservation are written inert)
     ctx->kstats["sk_scatter"].total_bytes += 0.25 * (double)r->n_bases + 18.0 * (double)n_desc;
@@ -2232,23 +1978,15 @@ std::shared_ptr<NcAhead> nc_ahead_begin(mcaat_ctx *ctx, int k, uint64_t n_occ_es
     auto a = std::make_shared<NcAhead>();
     a->ctx = ctx;
     a->k = k;
-    a->P = sk_params(k);
+    a->P = sk_params(ctx, k, false);
     a->P.l2_bits = nc_fine_bits(ctx, n_occ_est) - 8;
-    if (knob_set(ctx, "nc.a_mini"))
-        a->P.mini = (uint32_t)std::min<int64_t>(kMiniMax, std::max<int64_t>(8, knob(ctx, "nc.a_mini", 1024))) & ~7u;
     a->bk = std::make_shared<NcBuckets>();
     a->bk->l2_bits = a->P.l2_bits;
     a->a_grid = (uint64_t)kAPerCu * ctx->n_cu;
     // node_counter_a's sizing, with more headroom for the estimate
-    const double dens = 2.0 / (a->P.w + 1);
-    const uint64_t est = (uint64_t)(1.12 * (dens * (double)n_occ_est + (double)n_items_est)) + 4096;
-    a->cap.assign(256, 0);
+    a->cap = l1_caps(ctx, a->P, a->a_grid, n_occ_est, n_items_est, 1.12);
     a->base.assign(257, 0);
-    for (int b = 0; b < 256; ++b) {
-        a->cap[b] = (est / 256 + 2 * a->a_grid * a->P.mini + 7) & ~7ull;
-        if (const int64_t fixed = knob(ctx, "nc.l1_slots", 0)) a->cap[b] = ((uint64_t)fixed + 7) & ~7ull;
-        a->base[b + 1] = a->base[b] + a->cap[b];
-    }
+    std::partial_sum(a->cap.begin(), a->cap.end(), a->base.begin() + 1);
     a->bk->data.alloc(a->base[256]);
     a->bk->sub.alloc(a->base[256]);
     a->dcap.alloc(256);
@@ -2306,19 +2044,10 @@ std::shared_ptr<NcBuckets> nc_ahead_end(NcAhead &a) {
     if (a.failed) return nullptr;
     NcBuckets &bk = *a.bk;
     bk.n_occ = a.n_occ;
-    bk.base = a.base;
-    bk.regions.assign(256, {});
-    uint64_t n_desc = 0;
-    for (int b = 0; b < 256; ++b) {
-        n_desc += tot[b];
-        if (tot[b]) bk.regions[b].push_back({a.base[b], tot[b]});
-    }
+    const uint64_t n_desc = set_regions(bk, a.base, tot);
     ctx->kstats["sk_scatter_ahead"].launches += a.launches + 1;
     ctx->kstats["sk_scatter_ahead"].total_bytes += 18.0 * (double)n_desc;
-    if (!a.n_occ) {  // node_counter_a's empty-input buckets
-        bk.data.alloc(1);
-        bk.sub.alloc(8);
-    }
+    if (!a.n_occ) alloc_empty(bk, false);  // as node_counter_a on an empty input
     return a.bk;
 }
 
@@ -2389,6 +2118,60 @@ void plan_b(mcaat_ctx *ctx, NcBuckets &bk, uint64_t n_desc, BPlan &pl) {
         kt.stop();
     }
 }
+
+// one group of consecutive L1 buckets [b0, b1): chunks [c0, c1) of the plan, fine partitions
+// [p0, p1), gn descriptors from gbase
+struct BGroup {
+    int b0, b1;
+    uint64_t c0, c1, p0, p1, gbase, gn;
+    DevBuf<uint4> fine;
+    DevBuf<uint32_t> finew;  // weighted: the multiplicities at the same fine-partition slots
+    hipEvent_t done = nullptr;
+};
+// the buckets cut into groups: as many as hold at most budget(b0) descriptors, one at least
+std::vector<BGroup> cut_groups(const BPlan &pl, uint32_t S, const std::function<uint64_t(int)> &budget) {
+    std::vector<BGroup> groups;
+    for (int b0 = 0, b1; b0 < 256; b0 = b1) {
+        const uint64_t gb = budget(b0), p0 = (uint64_t)b0 * S;
+        for (b1 = b0 + 1; b1 < 256 && pl.hfine[(uint64_t)(b1 + 1) * S] - pl.hfine[p0] <= gb;) ++b1;
+        const uint64_t p1 = (uint64_t)b1 * S;
+        groups.push_back(BGroup{b0, b1, pl.bchunk[b0], pl.bchunk[b1], p0, p1, pl.hfine[p0], pl.hfine[p1] - pl.hfine[p0], {}, {}, nullptr});
+    }
+    return groups;
+}
+
+// limits of the collapse and the count per edge-table tier (0: 4096 slots, 1: 6144, two
+// workgroups per CU both; 2: 8192, one), under the knobs nc.edge_cap, nc.desc_cap, nc.split_*
+struct CLimits {
+    uint32_t cap_max[3], dmax[3];
+    // bits of a partition's first class split: round 3's four-way split in the 4096-slot tier (C2:
+    // partitions far over it); two-way in the 8192-slot tier, whose overflowing partitions (C5)
+    // are mostly just over it, so halves fit and each re-read is half as many passes
+    uint32_t split_first[3], split_max;
+};
+CLimits c_limits(mcaat_ctx *ctx) {
+    const int64_t caps[3] = {kCapMax, kCapMaxMid, kCapMaxBig}, dmaxs[3] = {kDMax, kDMax, dcap_for(kCapBig) * 3 / 4};
+    CLimits L;
+    for (int t = 0; t < 3; ++t) {
+        L.cap_max[t] = (uint32_t)knob_clamped(ctx, "nc.edge_cap", caps[t], 1, caps[t]);
+        L.dmax[t] = (uint32_t)knob_clamped(ctx, "nc.desc_cap", dmaxs[t], 1, dmaxs[t]);
+        L.split_first[t] = (uint32_t)knob_clamped(ctx, "nc.split_first", t == 2 ? 1 : kSplitLg, 1, kSplitMax);
+    }
+    L.split_max = (uint32_t)knob_clamped(ctx, "nc.split_max", kSplitMax, 1, kSplitMax);
+    return L;
+}
+
+// the output buffers at new_cap entries, the n_out counted so far kept. The old buffers go back
+// to the arena here, with sync_before_free only once the copies out of them have finished
+void grow_output(mcaat_ctx *ctx, CountResult &out, uint64_t n_out, uint64_t new_cap, bool sync_before_free) {
+    DevBuf<uint64_t> k2(new_cap);
+    DevBuf<uint32_t> c2(new_cap);
+    HIP_OK(hipMemcpyAsync(k2.p, out.keys.p, 8 * n_out, hipMemcpyDeviceToDevice, ctx->stream));
+    HIP_OK(hipMemcpyAsync(c2.p, out.counts.p, 4 * n_out, hipMemcpyDeviceToDevice, ctx->stream));
+    if (sync_before_free) HIP_OK(hipStreamSynchronize(ctx->stream));
+    out.keys = std::move(k2);
+    out.counts = std::move(c2);
+}
 }  // namespace
 
 // The sender-side collapse of a sharded build (dist.preagg; kernels: k_desc_preagg above). Pass B
@@ -2413,9 +2196,7 @@ void node_counter_preagg(mcaat_ctx *ctx, NcBuckets &bk, int k, NcBuckets &out, u
             n_desc += rg.second;
         }
     if (n_desc == 0) {
-        out.data.alloc(1);
-        out.sub.alloc(8);
-        out.wgt.alloc(8);
+        alloc_empty(out, true);
         bk.data.release();
         bk.sub.release();
         return;
@@ -2424,7 +2205,6 @@ void node_counter_preagg(mcaat_ctx *ctx, NcBuckets &bk, int k, NcBuckets &out, u
     const uint64_t F = 256ull * S;
     BPlan plan;
     plan_b(ctx, bk, n_desc, plan);
-    const std::vector<uint64_t> &hfine = plan.hfine;
 
     // output regions: one per L1 bucket, its live descriptors rounded up to whole 8-slot groups
     DevBuf<unsigned long long> dlive(256), dcur(256), dstat(2);
@@ -2451,38 +2231,28 @@ void node_counter_preagg(mcaat_ctx *ctx, NcBuckets &bk, int k, NcBuckets &out, u
     out.sub.alloc(total ? total : 8);
     out.wgt.alloc(total ? total : 8);
 
-    const uint32_t dmax = (uint32_t)std::min<int64_t>(kDMax, std::max<int64_t>(1, knob(ctx, "nc.desc_cap", kDMax)));
-    const uint32_t split_first = (uint32_t)std::min<int64_t>(kSplitMax, std::max<int64_t>(1, knob(ctx, "nc.split_first", kSplitLg)));
-    const uint32_t split_max = (uint32_t)std::min<int64_t>(kSplitMax, std::max<int64_t>(1, knob(ctx, "nc.split_max", kSplitMax)));
+    const CLimits lim = c_limits(ctx);  // the 4096-slot tier's
     const uint64_t group_budget =
-        (uint64_t)knob(ctx, "nc.group_budget", (int64_t)std::max<uint64_t>(hfine[F] / 4 + 1, 1ULL << 28));  // descriptors per group
-    for (int b0 = 0; b0 < 256;) {
-        int b1 = b0 + 1;
-        while (b1 < 256 && hfine[(uint64_t)(b1 + 1) * S] - hfine[(uint64_t)b0 * S] <= group_budget) ++b1;
-        const uint64_t p0 = (uint64_t)b0 * S, p1 = (uint64_t)b1 * S;
-        const uint64_t gbase = hfine[p0], gn = hfine[p1] - gbase;
-        const uint64_t c0 = plan.bchunk[b0], c1 = plan.bchunk[b1];
-        if (gn) {
-            DevBuf<uint4> fine(gn);
-            {
-                KernelTimer kt(ctx, "preagg_partition", 32.0 * (double)gn);
-                hipLaunchKernelGGL(k_l2_scatter<false>, dim3((unsigned)(c1 - c0)), dim3(kBThreads), 0, st, bk.data.p,
-                                   plan.dcs.p + c0, plan.dcl.p + c0, (const uint32_t *)plan.druns.p + c0 * S, bk.l2_bits, E,
-                                   fine.p, gbase, (const uint32_t *)nullptr, (uint32_t *)nullptr);
-                LAUNCH_OK();
-                kt.stop();
-            }
-            {
-                KernelTimer kt(ctx, "desc_preagg", 16.0 * (double)gn);
-                const unsigned wg = (unsigned)std::min<uint64_t>(p1 - p0, (uint64_t)kCPerCu * ctx->n_cu);
-                hipLaunchKernelGGL(k_desc_preagg, dim3(wg), dim3(kPThreads), 0, st, fine.p, gbase, plan.dfine.p, p0, p1,
-                                   bk.l2_bits, out.data.p, out.sub.p, out.wgt.p, (const uint64_t *)drb.p,
-                                   (const uint64_t *)drc.p, dcur.p, dmax, split_first, split_max, dstat.p);
-                LAUNCH_OK();
-                kt.stop();  // waits for the launch: the group's buffer goes back after it
-            }
+        (uint64_t)knob(ctx, "nc.group_budget", (int64_t)std::max<uint64_t>(plan.hfine[F] / 4 + 1, 1ULL << 28));  // descriptors per group
+    for (BGroup &g : cut_groups(plan, S, [&](int) { return group_budget; })) {
+        if (!g.gn) continue;
+        g.fine.alloc(g.gn);
+        {
+            KernelTimer kt(ctx, "preagg_partition", 32.0 * (double)g.gn);
+            hipLaunchKernelGGL(k_l2_scatter<false>, dim3((unsigned)(g.c1 - g.c0)), dim3(kBThreads), 0, st, bk.data.p,
+                               plan.dcs.p + g.c0, plan.dcl.p + g.c0, (const uint32_t *)plan.druns.p + g.c0 * S, bk.l2_bits, E,
+                               g.fine.p, g.gbase, (const uint32_t *)nullptr, (uint32_t *)nullptr);
+            LAUNCH_OK();
+            kt.stop();
         }
-        b0 = b1;
+        KernelTimer kt(ctx, "desc_preagg", 16.0 * (double)g.gn);
+        const unsigned wg = (unsigned)std::min<uint64_t>(g.p1 - g.p0, (uint64_t)kCPerCu * ctx->n_cu);
+        hipLaunchKernelGGL(k_desc_preagg, dim3(wg), dim3(kPThreads), 0, st, g.fine.p, g.gbase, plan.dfine.p, g.p0, g.p1,
+                           bk.l2_bits, out.data.p, out.sub.p, out.wgt.p, (const uint64_t *)drb.p,
+                           (const uint64_t *)drc.p, dcur.p, lim.dmax[0], lim.split_first[0], lim.split_max, dstat.p);
+        LAUNCH_OK();
+        kt.stop();  // waits for the launch: the group's buffer goes back after it
+        g.fine.release();
     }
     hipLaunchKernelGGL(k_preagg_pad, dim3(1), dim3(256), 0, st, out.data.p, out.sub.p, out.wgt.p, (const uint64_t *)drb.p,
                        (const uint64_t *)drc.p, (const unsigned long long *)dcur.p);
@@ -2518,12 +2288,7 @@ void node_counter_bc(mcaat_ctx *ctx, NcBuckets &bk, int k, CountResult &out) {
         out.counts.alloc(1);
         return;
     }
-    const uint64_t n_occ = bk.n_occ;
-    DevBuf<uint4> &l1 = bk.data;
-    DevBuf<uint16_t> &l1s = bk.sub;
-    SkParams P;
-    P.l2_bits = bk.l2_bits;
-    const uint32_t S = 1u << P.l2_bits;
+    const uint32_t S = 1u << bk.l2_bits;
     const uint64_t F = 256ull * S;
     DevBuf<unsigned long long> dprof(10);
 
@@ -2533,14 +2298,12 @@ void node_counter_bc(mcaat_ctx *ctx, NcBuckets &bk, int k, CountResult &out) {
     // footprint is the L1 buckets plus one group's fine partitions.
     BPlan plan;
     plan_b(ctx, bk, n_desc, plan);
-    const std::vector<uint64_t> &bchunk = plan.bchunk, &hfine = plan.hfine;
-    DevBuf<uint64_t> &dcs = plan.dcs, &dfine = plan.dfine;
-    DevBuf<uint32_t> &dcl = plan.dcl, &druns = plan.druns;
+    const std::vector<uint64_t> &hfine = plan.hfine;
     const bool weighted = bk.wgt.p != nullptr;  // (descriptor, multiplicity) records: dist.preagg
     const uint64_t n_live = hfine[F];
     verbose_mark(ctx, "node_counter.B_hist");
 
-    uint64_t out_cap = (uint64_t)knob(ctx, "nc.out_cap", (int64_t)std::max<uint64_t>(n_occ / 32, 1u << 20));
+    uint64_t out_cap = (uint64_t)knob(ctx, "nc.out_cap", (int64_t)std::max<uint64_t>(bk.n_occ / 32, 1u << 20));
     if (out_cap < 1) out_cap = 1;
     out.keys.alloc(out_cap);
     out.counts.alloc(out_cap);
@@ -2549,48 +2312,27 @@ void node_counter_bc(mcaat_ctx *ctx, NcBuckets &bk, int k, CountResult &out) {
     DevBuf<uint32_t> ovf_list(F << kSplitMax);  // one entry per (partition, class)
     static const bool prof_c = getenv("MCAAT_PROF_C") && getenv("MCAAT_PROF_C")[0] == '1';
     if (prof_c) HIP_OK(hipMemsetAsync(dprof.p, 0, dprof.bytes(), st));
-    const uint64_t group_budget =
-        (uint64_t)knob(ctx, "nc.group_budget", (int64_t)std::max<uint64_t>(n_live / 4 + 1, 1ULL << 28));  // descriptors per group
-    const uint32_t cap_max = (uint32_t)std::min<int64_t>(kCapMax, std::max<int64_t>(1, knob(ctx, "nc.edge_cap", kCapMax)));
-    const uint32_t cap_max_big = (uint32_t)std::min<int64_t>(kCapMaxBig, std::max<int64_t>(1, knob(ctx, "nc.edge_cap", kCapMaxBig)));
-    const uint32_t cap_max_mid = (uint32_t)std::min<int64_t>(kCapMaxMid, std::max<int64_t>(1, knob(ctx, "nc.edge_cap", kCapMaxMid)));
-    // larger edge tables: tier 0 = 4096 slots, 1 = 6144 (two workgroups per CU), 2 = 8192 (one).
-    // knob nc.big_table fixes the tier (0, 1 = 8192 as in round 3, 2 = 6144); default: from the
-    // next group on, 8192 slots once a group split more than 1 in 8 of its partitions into
-    // classes (error-rich data)
+    const CLimits lim = c_limits(ctx);
+    // knob nc.big_table fixes the edge-table tier (0, 1 = 8192 slots as in round 3, 2 = 6144);
+    // default: from the next group on, 8192 slots once a group split more than 1 in 8 of its
+    // partitions into classes (error-rich data)
     const int64_t big_knob = knob(ctx, "nc.big_table", -1);
     int tier = big_knob == 1 ? 2 : big_knob == 2 ? 1 : 0;
-    const uint32_t dmax = (uint32_t)std::min<int64_t>(kDMax, std::max<int64_t>(1, knob(ctx, "nc.desc_cap", kDMax)));
-    constexpr int kDMaxBig = dcap_for(kCapBig) * 3 / 4;
-    // bits of a partition's first class split: round 3's four-way split in the 4096-slot tier (C2:
-    // partitions far over it); two-way in the 8192-slot tier, whose overflowing partitions (C5)
-    // are mostly just over it, so halves fit and each re-read is half as many passes
-    const uint32_t split_first = (uint32_t)std::min<int64_t>(kSplitMax, std::max<int64_t>(1, knob(ctx, "nc.split_first", kSplitLg)));
-    const uint32_t split_big = (uint32_t)std::min<int64_t>(kSplitMax, std::max<int64_t>(1, knob(ctx, "nc.split_first", 1)));
-    const uint32_t split_max = (uint32_t)std::min<int64_t>(kSplitMax, std::max<int64_t>(1, knob(ctx, "nc.split_max", kSplitMax)));
-    const uint32_t dmax_big = (uint32_t)std::min<int64_t>(kDMaxBig, std::max<int64_t>(1, knob(ctx, "nc.desc_cap", kDMaxBig)));
     // groups of L1 buckets; with the overlap knob (default on) group g+1's pass B runs on the
     // side stream while group g's pass C counts on the main stream (two groups' fine
     // partitions alive at once, so groups are half the size)
     const bool overlap = knob(ctx, "nc.overlap", 1) != 0;
     const bool free_sync = knob(ctx, "nc.free_sync", 0) != 0;
-    struct Group {
-        int b0, b1;
-        DevBuf<uint4> fine;
-        hipEvent_t done = nullptr;
-        DevBuf<uint32_t> finew;  // weighted: the multiplicities at the same fine-partition slots
-    };
-    std::vector<Group> groups;
-    for (int b0 = 0; b0 < 256;) {
-        int b1 = b0 + 1;
-        uint64_t gb = overlap && !knob_set(ctx, "nc.group_budget") ? group_budget / 2 + 1 : group_budget;
+    const bool budget_set = knob_set(ctx, "nc.group_budget");
+    const uint64_t group_budget =
+        (uint64_t)knob(ctx, "nc.group_budget", (int64_t)std::max<uint64_t>(n_live / 4 + 1, 1ULL << 28));  // descriptors per group
+    auto budget = [&](int first) {
+        const uint64_t gb = overlap && !budget_set ? group_budget / 2 + 1 : group_budget;
         // the first group is a small probe: the edge-table tier is chosen from its class splits,
         // so on error-rich data only 1/16 of the descriptors take the re-read of a split
-        if (b0 == 0 && big_knob < 0 && !knob_set(ctx, "nc.group_budget")) gb = gb / 8 + 1;
-        while (b1 < 256 && hfine[(uint64_t)(b1 + 1) * S] - hfine[(uint64_t)b0 * S] <= gb) ++b1;
-        groups.push_back(Group{b0, b1, {}, nullptr});
-        b0 = b1;
-    }
+        return first == 0 && big_knob < 0 && !budget_set ? gb / 8 + 1 : gb;
+    };
+    std::vector<BGroup> groups = cut_groups(plan, S, budget);
     if (overlap && !ctx->side) HIP_OK(hipStreamCreateWithFlags(&ctx->side, hipStreamNonBlocking));
     hipStream_t sb = overlap ? ctx->side : st;
     if (overlap) {  // the side stream starts after everything queued so far (pass A, offsets)
@@ -2599,64 +2341,107 @@ void node_counter_bc(mcaat_ctx *ctx, NcBuckets &bk, int k, CountResult &out) {
         HIP_OK(hipStreamWaitEvent(sb, ev, 0));
         event_put(ctx, ev);
     }
-    std::vector<KernelTimer *> btimers;
-    auto launch_b = [&](Group &g) {
-        const uint64_t p0 = (uint64_t)g.b0 * S, p1 = (uint64_t)g.b1 * S;
-        const uint64_t gbase = hfine[p0], gn = hfine[p1] - gbase;
-        const uint64_t c0 = bchunk[g.b0], c1 = bchunk[g.b1];
+    std::vector<std::unique_ptr<KernelTimer>> btimers;  // of the launched B passes
+    auto launch_b = [&](BGroup &g) {
         {
             AllocStreamScope scope(sb);  // written by pass B on the side stream
-            g.fine.alloc(gn ? gn : 1);
-            if (weighted) g.finew.alloc(gn ? gn : 1);
+            g.fine.alloc(g.gn ? g.gn : 1);
+            if (weighted) g.finew.alloc(g.gn ? g.gn : 1);
         }
-        auto *kt = new KernelTimer(ctx, "l2_partition", 32.0 * (double)gn, sb);  // descriptors read, descriptors written
-        if (c1 > c0) {
-            hipLaunchKernelGGL(weighted ? k_l2_scatter<true> : k_l2_scatter<false>, dim3((unsigned)(c1 - c0)),
-                               dim3(kBThreads), 0, sb, l1.p, dcs.p + c0, dcl.p + c0,
-                               (const uint32_t *)druns.p + c0 * S, P.l2_bits, E, g.fine.p, gbase,
+        // descriptors read, descriptors written
+        btimers.push_back(std::make_unique<KernelTimer>(ctx, "l2_partition", 32.0 * (double)g.gn, sb));
+        if (g.c1 > g.c0) {
+            hipLaunchKernelGGL(weighted ? k_l2_scatter<true> : k_l2_scatter<false>, dim3((unsigned)(g.c1 - g.c0)),
+                               dim3(kBThreads), 0, sb, bk.data.p, plan.dcs.p + g.c0, plan.dcl.p + g.c0,
+                               (const uint32_t *)plan.druns.p + g.c0 * S, bk.l2_bits, E, g.fine.p, g.gbase,
                                (const uint32_t *)bk.wgt.p, g.finew.p);
             LAUNCH_OK();
         }
-        kt->mark();
+        btimers.back()->mark();
         g.done = event_get(ctx);
         HIP_OK(hipEventRecord(g.done, sb));
-        btimers.push_back(kt);
     };
-    struct TimerGuard {  // timers of launched B passes, freed on every exit
-        std::vector<KernelTimer *> &v;
-        ~TimerGuard() { for (auto *t : v) delete t; }
-    } tguard{btimers};
+    // pass C's kernel by [weighted][2 - tier][!prof] (the rows in the kernels' order in the code object)
+    using CKernel = decltype(&k_lds_count<true, kCapBig, 1, false>);
+    static const CKernel c_kernels[2][3][2] = {
+        {{k_lds_count<true, kCapBig, 1, false>, k_lds_count<false, kCapBig, 1, false>},
+         {k_lds_count<true, kCapMid, kCPerCu, false>, k_lds_count<false, kCapMid, kCPerCu, false>},
+         {k_lds_count<true, kCap, kCPerCu, false>, k_lds_count<false, kCap, kCPerCu, false>}},
+        {{k_lds_count<true, kCapBig, 1, true>, k_lds_count<false, kCapBig, 1, true>},
+         {k_lds_count<true, kCapMid, kCPerCu, true>, k_lds_count<false, kCapMid, kCPerCu, true>},
+         {k_lds_count<true, kCap, kCPerCu, true>, k_lds_count<false, kCap, kCPerCu, true>}}};
+    auto launch_c = [&](int tier, const BGroup &g) {
+        KernelTimer kt(ctx, "lds_count", 16.0 * (double)g.gn);
+        const unsigned wg = (unsigned)std::min<uint64_t>(g.p1 - g.p0, (uint64_t)(tier == 2 ? 1 : kCPerCu) * ctx->n_cu);
+        hipLaunchKernelGGL(c_kernels[weighted][2 - tier][!prof_c], dim3(wg), dim3(kCThreads), 0, st, g.fine.p, g.gbase,
+                           plan.dfine.p, g.p0, g.p1, E, out.keys.p, out.counts.p, out_cap, dcnt.p, ovf_list.p, dcnt.p + 1,
+                           lim.cap_max[tier], lim.dmax[tier], dcnt.p + 2, lim.split_first[tier], lim.split_max,
+                           prof_c ? dprof.p : nullptr, (const uint32_t *)g.finew.p);
+        LAUNCH_OK();
+        kt.stop();
+    };
+    // global-table fallback for the n_ovf (partition, class) entries of ovf_list whose distinct edges
+    // overflowed LDS, in batches whose table fits a fixed memory budget; returns the output cursor after it
+    auto count_overflowed = [&](const BGroup &g, uint64_t n_ovf) -> uint64_t {
+        const uint32_t *wgt = g.finew.p;  // set: (descriptor, multiplicity) records
+        DevBuf<uint64_t> occ(n_ovf);
+        hipLaunchKernelGGL(wgt ? k_part_occ<true> : k_part_occ<false>, dim3((unsigned)std::min<uint64_t>(n_ovf, 65536)),
+                           dim3(kBlock), 0, st, g.fine.p, g.gbase, plan.dfine.p, ovf_list.p, n_ovf, occ.p, wgt);
+        LAUNCH_OK();
+        std::vector<uint64_t> occ_h(n_ovf);
+        std::vector<uint32_t> parts_h(n_ovf);
+        d2h(ctx, occ_h.data(), occ.p, 8 * n_ovf);
+        d2h(ctx, parts_h.data(), ovf_list.p, 4 * n_ovf);
+        const uint64_t occ_max =
+            (uint64_t)std::max<int64_t>(1, knob(ctx, "nc.fallback_budget", 1LL << 30));  // occurrences per batch (table <= 32 GB)
+        DevBuf<unsigned long long> nn(1);
+        DevBuf<int> dover(1);
+        DevBuf<uint32_t> dparts(n_ovf);
+        for (uint64_t q0 = 0; q0 < n_ovf;) {
+            uint64_t q1 = q0, occ_b = 0;
+            while (q1 < n_ovf && (q1 == q0 || occ_b + occ_h[q1] <= occ_max)) occ_b += occ_h[q1++];
+            HIP_OK(hipMemcpyAsync(dparts.p, parts_h.data() + q0, 4 * (q1 - q0), hipMemcpyHostToDevice, st));
+            uint64_t tcap = next_pow2(occ_b + occ_b / 2 + 1024);
+            for (;;) {
+                DevBuf<Slot> tab(tcap);
+                HIP_OK(hipMemsetAsync(tab.p, 0, tab.bytes(), st));
+                HIP_OK(hipMemsetAsync(nn.p, 0, 8, st));
+                HIP_OK(hipMemsetAsync(dover.p, 0, 4, st));
+                hipLaunchKernelGGL(wgt ? k_fallback<true> : k_fallback<false>,
+                                   dim3((unsigned)std::min<uint64_t>(q1 - q0, 65536)), dim3(kBlock), 0, st, g.fine.p, g.gbase,
+                                   plan.dfine.p, dparts.p, q1 - q0, E, tab.p, tcap - 1, nn.p, dover.p, wgt);
+                LAUNCH_OK();
+                int over = 0;
+                HIP_OK(hipMemcpyAsync(&over, dover.p, 4, hipMemcpyDeviceToHost, st));
+                HIP_OK(hipStreamSynchronize(st));
+                if (over) {
+                    tcap <<= 1;
+                    continue;
+                }
+                hipLaunchKernelGGL(k_fallback_emit, dim3(grid_for(tcap, kBlock, 65536)), dim3(kBlock), 0, st, tab.p, tcap,
+                                   out.keys.p, out.counts.p, out_cap, dcnt.p);
+                LAUNCH_OK();
+                HIP_OK(hipStreamSynchronize(st));
+                break;
+            }
+            q0 = q1;
+        }
+        unsigned long long total = 0;
+        HIP_OK(hipMemcpyAsync(&total, dcnt.p, 8, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        return total;
+    };
     uint64_t n_out = 0;
     if (!groups.empty()) launch_b(groups[0]);
     for (size_t gi = 0; gi < groups.size(); ++gi) {
-        Group &grp = groups[gi];
-        const int b0 = grp.b0, b1 = grp.b1;
-        const uint64_t p0 = (uint64_t)b0 * S, p1 = (uint64_t)b1 * S;
-        const uint64_t gbase = hfine[p0], gn = hfine[p1] - gbase;
+        BGroup &grp = groups[gi];
         HIP_OK(hipStreamWaitEvent(st, grp.done, 0));
         // the next group's partitioning overlaps this group's counting
         if (overlap && gi + 1 < groups.size()) launch_b(groups[gi + 1]);
-        DevBuf<uint4> &fine = grp.fine;
         // C; a group whose output overflows the key buffers is counted again after they grow
         for (int attempt = 0;; ++attempt) {
             HIP_OK(hipMemsetAsync(dcnt.p + 1, 0, 16, st));
-            {
-                KernelTimer kt(ctx, "lds_count", 16.0 * (double)gn);
-                const unsigned wg = (unsigned)std::min<uint64_t>(p1 - p0, (uint64_t)(tier == 2 ? 1 : kCPerCu) * ctx->n_cu);
-                auto kern_u = tier == 2 ? (prof_c ? k_lds_count<true, kCapBig, 1, false> : k_lds_count<false, kCapBig, 1, false>)
-                            : tier == 1 ? (prof_c ? k_lds_count<true, kCapMid, kCPerCu, false> : k_lds_count<false, kCapMid, kCPerCu, false>)
-                                  : (prof_c ? k_lds_count<true, kCap, kCPerCu, false> : k_lds_count<false, kCap, kCPerCu, false>);
-                auto kern_w = tier == 2 ? (prof_c ? k_lds_count<true, kCapBig, 1, true> : k_lds_count<false, kCapBig, 1, true>)
-                            : tier == 1 ? (prof_c ? k_lds_count<true, kCapMid, kCPerCu, true> : k_lds_count<false, kCapMid, kCPerCu, true>)
-                                  : (prof_c ? k_lds_count<true, kCap, kCPerCu, true> : k_lds_count<false, kCap, kCPerCu, true>);
-                hipLaunchKernelGGL(weighted ? kern_w : kern_u, dim3(wg), dim3(kCThreads), 0, st, fine.p, gbase, dfine.p, p0, p1, E, out.keys.p,
-                                   out.counts.p, out_cap, dcnt.p, ovf_list.p, dcnt.p + 1,
-                                   tier == 2 ? cap_max_big : tier == 1 ? cap_max_mid : cap_max, tier == 2 ? dmax_big : dmax,
-                                   dcnt.p + 2, tier == 2 ? split_big : split_first, split_max, prof_c ? dprof.p : nullptr,
-                                   (const uint32_t *)grp.finew.p);
-                LAUNCH_OK();
-                kt.stop();
-            }
+            launch_c(tier, grp);
             unsigned long long hc[3];
             HIP_OK(hipMemcpyAsync(hc, dcnt.p, 24, hipMemcpyDeviceToHost, st));
             HIP_OK(hipStreamSynchronize(st));
@@ -2664,77 +2449,21 @@ void node_counter_bc(mcaat_ctx *ctx, NcBuckets &bk, int k, CountResult &out) {
             ctx->kstats["lds_count_split_partitions"].launches += hc[2];
             // measured at C5: the 6144-slot tier still splits more than 1 in 8 partitions (183.6 ms
             // of pass C either way), so the default goes straight to 8192 slots
-            if (big_knob < 0 && tier < 2 && hc[2] * 8 > p1 - p0) tier = 2;
+            if (big_knob < 0 && tier < 2 && hc[2] * 8 > grp.p1 - grp.p0) tier = 2;
             ctx->kstats["lds_count_overflow_partitions"].launches += n_ovf;
-            if (n_ovf) {
-                // global-table fallback for the partitions whose distinct edges overflowed LDS,
-                // in batches whose table fits a fixed memory budget
-                DevBuf<uint64_t> occ(n_ovf);
-                hipLaunchKernelGGL(weighted ? k_part_occ<true> : k_part_occ<false>,
-                                   dim3((unsigned)std::min<uint64_t>(n_ovf, 65536)), dim3(kBlock), 0, st, fine.p, gbase,
-                                   dfine.p, ovf_list.p, n_ovf, occ.p, (const uint32_t *)grp.finew.p);
-                LAUNCH_OK();
-                std::vector<uint64_t> occ_h(n_ovf);
-                std::vector<uint32_t> parts_h(n_ovf);
-                d2h(ctx, occ_h.data(), occ.p, 8 * n_ovf);
-                d2h(ctx, parts_h.data(), ovf_list.p, 4 * n_ovf);
-                const uint64_t budget =
-                    (uint64_t)std::max<int64_t>(1, knob(ctx, "nc.fallback_budget", 1LL << 30));  // occurrences per batch (table <= 32 GB)
-                DevBuf<unsigned long long> nn(1);
-                DevBuf<int> dover(1);
-                DevBuf<uint32_t> dparts(n_ovf);
-                for (uint64_t q0 = 0; q0 < n_ovf;) {
-                    uint64_t q1 = q0, occ_b = 0;
-                    while (q1 < n_ovf && (q1 == q0 || occ_b + occ_h[q1] <= budget)) occ_b += occ_h[q1++];
-                    HIP_OK(hipMemcpyAsync(dparts.p, parts_h.data() + q0, 4 * (q1 - q0), hipMemcpyHostToDevice, st));
-                    uint64_t tcap = next_pow2(occ_b + occ_b / 2 + 1024);
-                    for (;;) {
-                        DevBuf<Slot> tab(tcap);
-                        HIP_OK(hipMemsetAsync(tab.p, 0, tab.bytes(), st));
-                        HIP_OK(hipMemsetAsync(nn.p, 0, 8, st));
-                        HIP_OK(hipMemsetAsync(dover.p, 0, 4, st));
-                        hipLaunchKernelGGL(weighted ? k_fallback<true> : k_fallback<false>,
-                                           dim3((unsigned)std::min<uint64_t>(q1 - q0, 65536)), dim3(kBlock), 0, st, fine.p,
-                                           gbase, dfine.p, dparts.p, q1 - q0, E, tab.p, tcap - 1, nn.p, dover.p,
-                                           (const uint32_t *)grp.finew.p);
-                        LAUNCH_OK();
-                        int over = 0;
-                        HIP_OK(hipMemcpyAsync(&over, dover.p, 4, hipMemcpyDeviceToHost, st));
-                        HIP_OK(hipStreamSynchronize(st));
-                        if (over) {
-                            tcap <<= 1;
-                            continue;
-                        }
-                        hipLaunchKernelGGL(k_fallback_emit, dim3(grid_for(tcap, kBlock, 65536)), dim3(kBlock), 0, st,
-                                           tab.p, tcap, out.keys.p, out.counts.p, out_cap, dcnt.p);
-                        LAUNCH_OK();
-                        HIP_OK(hipStreamSynchronize(st));
-                        break;
-                    }
-                    q0 = q1;
-                }
-                HIP_OK(hipMemcpyAsync(hc, dcnt.p, 8, hipMemcpyDeviceToHost, st));
-                HIP_OK(hipStreamSynchronize(st));
-            }
-            const uint64_t total = hc[0];
+            const uint64_t total = n_ovf ? count_overflowed(grp, n_ovf) : hc[0];
             ctx->kstats["lds_count"].total_bytes += 12.0 * (double)(std::min(total, out_cap) - std::min(n_out, out_cap));
             if (total <= out_cap) {
                 n_out = total;
                 break;
             }
             if (attempt > 0) throw Error(MCAAT_E_CAPACITY, "node_counter: output sizing failed");
-            if (getenv("MCAAT_VERBOSE") && getenv("MCAAT_VERBOSE")[0] == '1')
+            if (verbose_on())
                 fprintf(stderr, "[mcaat] node_counter: group %zu overflowed the output (%llu > %llu): re-count\n", gi,
                         (unsigned long long)total, (unsigned long long)out_cap);
             // grow (keeping the groups already counted) and count this group again
-            const uint64_t ncap = total + (total - n_out) * (uint64_t)(256 - b1) / (uint64_t)(b1 - b0) + (1u << 20);
-            DevBuf<uint64_t> k2(ncap);
-            DevBuf<uint32_t> c2(ncap);
-            HIP_OK(hipMemcpyAsync(k2.p, out.keys.p, 8 * n_out, hipMemcpyDeviceToDevice, st));
-            HIP_OK(hipMemcpyAsync(c2.p, out.counts.p, 4 * n_out, hipMemcpyDeviceToDevice, st));
-            out.keys = std::move(k2);
-            out.counts = std::move(c2);
-            out_cap = ncap;
+            out_cap = total + (total - n_out) * (uint64_t)(256 - grp.b1) / (uint64_t)(grp.b1 - grp.b0) + (1u << 20);
+            grow_output(ctx, out, n_out, out_cap, false);
             // the counter restarts at n_out (two 32-bit device writes: no host buffer to keep alive)
             HIP_OK(hipMemsetD32Async((hipDeviceptr_t)dcnt.p, (int)(uint32_t)n_out, 1, st));
             HIP_OK(hipMemsetD32Async((hipDeviceptr_t)((uint32_t *)dcnt.p + 1), (int)(uint32_t)(n_out >> 32), 1, st));
@@ -2746,35 +2475,29 @@ void node_counter_bc(mcaat_ctx *ctx, NcBuckets &bk, int k, CountResult &out) {
         // error-rich input (C5: ~2 G) used to overflow it mid-run, re-count a whole group and copy
         // everything counted so far. The groups are hash ranges, so the first (the small probe)
         // already tells the total: grow once, early, while little is copied.
-        if (gi + 1 < groups.size() && (!knob_set(ctx, "nc.out_cap") || knob(ctx, "nc.grow_early", 0)) && hfine[p1] > 0) {
-            const double frac = (double)hfine[p1] / (double)std::max<uint64_t>(n_live, 1);
+        if (gi + 1 < groups.size() && (!knob_set(ctx, "nc.out_cap") || knob(ctx, "nc.grow_early", 0)) && hfine[grp.p1] > 0) {
+            const double frac = (double)hfine[grp.p1] / (double)std::max<uint64_t>(n_live, 1);
             // grown with 8 % headroom, and again only when the plain extrapolation passes that
             // (C5's estimate moved 2.1194 -> 2.1201 G over the groups: three copies of up to 9 GB)
             const double need = (double)n_out / frac;
             const uint64_t est = (uint64_t)(need * 1.08) + (1u << 20);
             if (need > (double)out_cap) {
-                if (getenv("MCAAT_VERBOSE") && getenv("MCAAT_VERBOSE")[0] == '1')
+                if (verbose_on())
                     fprintf(stderr, "[mcaat] node_counter: output grown after group %zu (%llu distinct, %.4f of the descriptors): %llu -> %llu\n",
                             gi, (unsigned long long)n_out, frac, (unsigned long long)out_cap, (unsigned long long)est);
-                DevBuf<uint64_t> k2(est);
-                DevBuf<uint32_t> c2(est);
-                HIP_OK(hipMemcpyAsync(k2.p, out.keys.p, 8 * n_out, hipMemcpyDeviceToDevice, st));
-                HIP_OK(hipMemcpyAsync(c2.p, out.counts.p, 4 * n_out, hipMemcpyDeviceToDevice, st));
                 // the next group's pass B (side stream) may be handed the old buffers: the arena
-                // makes it wait for these copies (round 4 synchronised here: nc.free_sync=1)
-                if (free_sync) HIP_OK(hipStreamSynchronize(st));
-                out.keys = std::move(k2);
-                out.counts = std::move(c2);
+                // makes it wait for the copies (round 4 synchronised before freeing them: nc.free_sync=1)
+                grow_output(ctx, out, n_out, est, free_sync);
                 out_cap = est;
             }
         }
         if (!overlap && gi + 1 < groups.size()) launch_b(groups[gi + 1]);
-        fine.release();
+        grp.fine.release();
         grp.finew.release();
         event_put(ctx, grp.done);
         grp.done = nullptr;
     }
-    for (auto *t : btimers) t->finish();
+    for (auto &t : btimers) t->finish();
     if (prof_c) {
         unsigned long long hp[10];
         HIP_OK(hipMemcpy(hp, dprof.p, 80, hipMemcpyDeviceToHost));
@@ -2785,8 +2508,8 @@ void node_counter_bc(mcaat_ctx *ctx, NcBuckets &bk, int k, CountResult &out) {
         fprintf(stderr, "[mcaat] pass C expansion: %llu edge inserts for %llu distinct edges (%.2f per edge)\n", hp[8], hp[9],
                 hp[9] ? (double)hp[8] / (double)hp[9] : 0.0);
     }
-    l1.release();
-    l1s.release();
+    bk.data.release();
+    bk.sub.release();
     bk.wgt.release();
     bk.regions.assign(256, {});
     out.n = n_out;
