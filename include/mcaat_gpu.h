@@ -386,11 +386,6 @@ void mcaat_reset_timing(mcaat_ctx *ctx);
  *   cf.ruler_mask      1 in (mask + 1) unary nodes is a peel ruler besides the chain heads
  *   cf.fused_init      0: the peel's first pass as its own kernel (default 1: done by the tips /
  *                      multiplicity-filter pass)
- *   cf.recount         1: the valid / tips recount and ChunkStartNodes' candidate filter as
- *                      their own pass after the peel (default 0: the tips / filter pass lists the
- *                      post-filter candidates and counts the post-filter tips that are not
- *                      seeds; after the peel the candidates still valid are kept and the valid
- *                      bits are popcounted)
  *   cf.dls_host        1: DepthLevelSearch candidates and results through the host (default 0:
  *                      on one GPU they stay on the device and only the passing ids come back)
  *   cf.compact         1: the peel's per-edge arrays over compact slots of the filter-valid edges,

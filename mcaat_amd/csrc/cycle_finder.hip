@@ -205,39 +205,31 @@ __global__ void __launch_bounds__(kBlock) k_word_pop(const uint64_t *bm, uint64_
 // predecessor flags come out here instead of from a second streaming pass over out_info and
 // the filtered bitmap; with pa.wpre they go to the edges' compact slots (PeelArrays::cidx).
 // words [w_lo, w_hi) (a rank's share; all of them on one GPU)
-// With a candidate list (cand != nullptr) the pass also does the recount's work on the
-// post-filter graph (round 3): counts[2] post-filter tips that are not seeds (every one of them
-// survives the peel, and no surviving edge becomes a tip: the reduction removes every valid edge
-// whose successors it all removed), and ChunkStartNodes' filter on post-filter validity
-// (valid, mult > thr, at least two valid in-edges, not its own in-edge) into cand (counts[3]
-// counts them all). A removed edge had no valid successor, so the peel changes no surviving
-// edge's valid in-edges: the final candidates are these, still valid after the peel.
-// (round 5) fresh and pull are template parameters: the default form (fresh, no pull) then keeps
-// none of the other forms' registers (C3: 105 VGPRs, four waves per SIMD, in one kernel for all)
-template <int kScanU, bool kFresh, bool kPull>
-// fresh: every edge is valid before the filter (mcaat_graph::all_valid), so an edge is a tip
-// iff it has no out-edges at all, and no window of the unfiltered bitmap is read
-// pull (round 4, with the peel's arrays): an edge writes its own predecessor flags instead of
-// each predecessor setting a byte at its successors' slots. All predecessors of y share y's
-// source node, so their filtered out-degree is the number of filter-valid siblings of y (the
-// out-edges of that node: consecutive ids, and with any predecessor present exactly the ids
-// around y whose in_info word equals y's), and y has one iff its in-edge window holds a
-// filter-valid edge. One 4-byte store per edge, no scattered byte stores and no clearing pass.
+// The pass also does the recount's work on the post-filter graph: counts[2] post-filter tips
+// that are not seeds (every one of them survives the peel, and no surviving edge becomes a tip:
+// the reduction removes every valid edge whose successors it all removed), and ChunkStartNodes'
+// filter on post-filter validity (valid, mult > thr, at least two valid in-edges, not its own
+// in-edge) into cand (counts[3] counts them all). A removed edge had no valid successor, so the
+// peel changes no surviving edge's valid in-edges: the final candidates are these, still valid
+// after the peel.
+// kFresh: every edge is valid before the filter (mcaat_graph::all_valid), so an edge is a tip
+// iff it has no out-edges at all, and no window of the unfiltered bitmap is read; a template
+// parameter, so that the fresh form keeps none of the other's registers
+template <int kScanU, bool kFresh>
 __global__ void __launch_bounds__(kBlock) k_tips_filter(GraphView g, uint64_t w_lo, uint64_t w_hi, uint64_t *tip_bm,
                                                         const uint64_t *post, unsigned long long *counts, PeelArrays pa,
                                                         uint64_t thr, uint64_t *cand, uint64_t cap) {
     const int lane = threadIdx.x & 63;
     const uint64_t nw = (g.D + 63) / 64;
     const uint64_t wstride = ((uint64_t)gridDim.x * blockDim.x) >> 6;
-    const bool peel = pa.nf != nullptr, fold = cand != nullptr;
+    const bool peel = pa.nf != nullptr;
     constexpr bool fresh = kFresh;
-    const bool pull = kPull && peel;
     const unsigned long long lt = lane ? (~0ull >> (64 - lane)) : 0ull;
     __shared__ uint64_t cbuf[kBlock / 64][128];
     WaveList cl{cbuf[threadIdx.x >> 6], cand, counts + 3, cap};
     unsigned long long acc = 0, tips_pf = 0;
     for (uint64_t wb = w_lo + (((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6); wb < w_hi; wb += kScanU * wstride) {
-        uint64_t sv[kScanU], pv[kScanU], oi[kScanU], xb[kScanU];
+        uint64_t sv[kScanU], pv[kScanU], oi[kScanU];
         WordPair a[kScanU], a2[kScanU];
         uint32_t mu[kScanU];
 #pragma unroll
@@ -246,17 +238,7 @@ __global__ void __launch_bounds__(kBlock) k_tips_filter(GraphView g, uint64_t w_
             sv[u] = w < w_hi ? (fresh ? word_ones(w, g.D) : g.valid[w]) : 0;
             pv[u] = w < w_hi ? post[w] : 0;
             oi[u] = e < g.D && w < w_hi ? g.out_info[e] : 0;
-            mu[u] = e < g.D && w < w_hi && fold ? g.mult[e] : 0;
-            // pull: lanes 0..2 and 61..63 hold the in_info words of the 3 ids on either side of
-            // the word (0 unless filter-valid), for their neighbours' sibling counts
-            xb[u] = 0;
-            if (pull && w < w_hi && (lane < 3 || lane > 60)) {
-                const int64_t y = lane < 3 ? (int64_t)(w * 64) - 3 + lane : (int64_t)(w * 64) + 64 + (lane - 61);
-                if (y >= 0 && (uint64_t)y < g.D) {  // both loads issued together
-                    const uint64_t x = g.in_info[y], pw = post[(uint64_t)y >> 6];
-                    xb[u] = ((pw >> (y & 63)) & 1) ? x : 0;
-                }
-            }
+            mu[u] = e < g.D && w < w_hi ? g.mult[e] : 0;
         }
         uint64_t ii[kScanU];
         WordPair b[kScanU];
@@ -264,39 +246,15 @@ __global__ void __launch_bounds__(kBlock) k_tips_filter(GraphView g, uint64_t w_
         for (int u = 0; u < kScanU; ++u) {
             const uint64_t w = wb + u * wstride, e = w * 64 + lane;
             // the candidate filter's in-edge window, for post-filter valid edges above thr
-            const bool cv = e < g.D && w < w_hi && ((pv[u] >> lane) & 1) && (pull || (fold && (uint64_t)mu[u] > thr));
+            const bool cv = e < g.D && w < w_hi && ((pv[u] >> lane) & 1) && (uint64_t)mu[u] > thr;
             ii[u] = cv ? g.in_info[e] : 0;
         }
 #pragma unroll
         for (int u = 0; u < kScanU; ++u) {
             const uint64_t lo = oi[u] & kIdxMask;
             if (!fresh) a[u] = word_pair(g.valid, lo, nw);
-            if (peel || fold) a2[u] = word_pair(post, lo, nw);
-            if (fold || pull) b[u] = word_pair(post, ii[u] & kIdxMask, nw);
-        }
-        // pull: filter-valid siblings of each edge (equal in_info words within 3 ids); the ids
-        // outside the wave's word come from the neighbouring words, read only by the lanes at
-        // its ends that need them
-        uint32_t sib[kScanU];
-        if (pull) {
-#pragma unroll
-            for (int u = 0; u < kScanU; ++u) {
-                const uint64_t w = wb + u * wstride, e = w * 64 + lane;
-                const uint64_t my = ii[u];
-                uint32_t c = 0;
-#pragma unroll
-                for (int d = -3; d <= 3; ++d) {
-                    if (!d) continue;
-                    const int nl = lane + d;
-                    // every lane shuffles (uniform): the neighbour's word from its lane, or from the
-                    // lane holding that id outside the word (xb, loaded with the scan's other loads)
-                    const uint64_t x = __shfl(my, nl & 63);
-                    const uint64_t xo = __shfl(xb[u], nl < 0 ? nl + 3 : (nl - 64 + 61) & 63);
-                    c += (nl >= 0 && nl < 64 ? x : xo) == my;
-                }
-                (void)e;
-                sib[u] = c + 1;  // and the edge itself
-            }
+            a2[u] = word_pair(post, lo, nw);
+            b[u] = word_pair(post, ii[u] & kIdxMask, nw);
         }
 #pragma unroll
         for (int u = 0; u < kScanU; ++u) {
@@ -311,61 +269,49 @@ __global__ void __launch_bounds__(kBlock) k_tips_filter(GraphView g, uint64_t w_
                 acc += __popcll(m);
             }
             const bool vpf = e < g.D && w < w_hi && ((pv[u] >> lane) & 1);  // valid after the filter
-            const unsigned pfo = (peel || fold) ? bits16(a2[u].a, a2[u].b, lo) & ((1u << cnt) - 1) : 0;  // successors valid after it
-            if (fold) {
-                // a post-filter tip that is not a seed (t: a pre-filter tip, i.e. a seed)
-                const unsigned long long tpm = __ballot(vpf && pfo == 0 && !t);
-                if (lane == 0) tips_pf += __popcll(tpm);
-                bool c = false;
-                if (vpf && (uint64_t)mu[u] > thr) {
-                    const uint64_t l = ii[u] & kIdxMask;
-                    const unsigned in = bits16(b[u].a, b[u].b, l) & (uint32_t)((ii[u] >> kIdxBits) & 0xFFFF);  // post-filter valid in-edges
-                    const bool self = e >= l && e - l < 16 && ((in >> (e - l)) & 1);
-                    c = __popc(in) >= 2 && !self;
-                }
-                cl.push(c, e);
+            const unsigned pfo = bits16(a2[u].a, a2[u].b, lo) & ((1u << cnt) - 1);  // successors valid after it
+            // a post-filter tip that is not a seed (t: a pre-filter tip, i.e. a seed)
+            const unsigned long long tpm = __ballot(vpf && pfo == 0 && !t);
+            if (lane == 0) tips_pf += __popcll(tpm);
+            bool c = false;
+            if (vpf && (uint64_t)mu[u] > thr) {
+                const uint64_t l = ii[u] & kIdxMask;
+                const unsigned in = bits16(b[u].a, b[u].b, l) & (uint32_t)((ii[u] >> kIdxBits) & 0xFFFF);  // post-filter valid in-edges
+                const bool self = e >= l && e - l < 16 && ((in >> (e - l)) & 1);
+                c = __popc(in) >= 2 && !self;
             }
+            cl.push(c, e);
             // (an edge invalid after the filter gets no kind byte: prep reads the filtered bitmap
             // first, and every other pass reaches only valid edges)
-            if (peel && e < g.D && w < w_hi) {
-                if (vpf) {
-                    const uint64_t ce = pa.wpre ? (uint64_t)pa.wpre[w] + __popcll(pv[u] & lt) : e;
-                    // compact slot of successor lo + i: its word is lo's or the next one
-                    auto cs = [&](int i) -> uint64_t {
-                        const uint64_t y = lo + i;
-                        if (!pa.wpre) return y;
-                        const uint64_t wy = y >> 6;
-                        const uint64_t pw = wy == this_word(lo, nw) ? a2[u].a : a2[u].b;
-                        return (uint64_t)pa.wpre[wy] + __popcll(pw & ((1ull << (y & 63)) - 1));
-                    };
-                    int od = 0, i1 = -1;
-                    for (int i = (int)cnt - 1; i >= 0; --i)  // descending ids, as dev_outgoing
-                        if ((pfo >> i) & 1) {
-                            ++od;
-                            i1 = i;
-                        }
-                    if (pull) {
-                        const uint64_t l = ii[u] & kIdxMask;
-                        const bool haspred = (bits16(b[u].a, b[u].b, l) & (uint32_t)((ii[u] >> kIdxBits) & 0xFFFF)) != 0;
-                        const uint32_t up = haspred && sib[u] == 1, bp = haspred && sib[u] >= 2;
-                        *(uint32_t *)(pa.nf + 4 * ce) = (uint32_t)od | (up << (8 * kFUpred)) | (bp << (8 * kFBpred));
-                        if (od == 1) pa.nxk[ce] = cs(i1);
-                    } else {
-                        pa.kind(ce) = (uint8_t)od;
-                        if (od == 1) {
-                            const uint64_t cy = cs(i1);
-                            pa.nxk[ce] = cy;
-                            pa.upred(cy) = 1;
-                        } else {
-                            for (int i = (int)cnt - 1; i >= 0; --i)
-                                if ((pfo >> i) & 1) pa.bpred(cs(i)) = 1;
-                        }
+            if (peel && vpf) {
+                const uint64_t ce = pa.wpre ? (uint64_t)pa.wpre[w] + __popcll(pv[u] & lt) : e;
+                // compact slot of successor lo + i: its word is lo's or the next one
+                auto cs = [&](int i) -> uint64_t {
+                    const uint64_t y = lo + i;
+                    if (!pa.wpre) return y;
+                    const uint64_t wy = y >> 6;
+                    const uint64_t pw = wy == this_word(lo, nw) ? a2[u].a : a2[u].b;
+                    return (uint64_t)pa.wpre[wy] + __popcll(pw & ((1ull << (y & 63)) - 1));
+                };
+                int od = 0, i1 = -1;
+                for (int i = (int)cnt - 1; i >= 0; --i)  // descending ids, as dev_outgoing
+                    if ((pfo >> i) & 1) {
+                        ++od;
+                        i1 = i;
                     }
+                pa.kind(ce) = (uint8_t)od;
+                if (od == 1) {
+                    const uint64_t cy = cs(i1);
+                    pa.nxk[ce] = cy;
+                    pa.upred(cy) = 1;
+                } else {
+                    for (int i = (int)cnt - 1; i >= 0; --i)
+                        if ((pfo >> i) & 1) pa.bpred(cs(i)) = 1;
                 }
             }
         }
     }
-    if (fold) cl.finish();
+    cl.finish();
     block_add(counts, acc);
     block_add(counts + 2, tips_pf);
 }
@@ -384,65 +330,6 @@ __global__ void __launch_bounds__(kBlock) k_still_valid(const uint64_t *bm, cons
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) f[i] = bit_get(bm, ids[i]);
 }
-
-// the recount after the reduction (valid edges, tips) and ChunkStartNodes' candidate filter in
-// one pass: counts[0] valid, counts[1] tips (whole graph), candidates only in [lo, hi) (a rank's
-// share), appended to list while they fit in cap (counts[2] counts them all)
-// the words covering ids [lo, hi) (a rank's share; all of them on one GPU): counts over those
-// words (summed over the ranks), candidates among ids [lo, hi)
-template <int kScanU>
-__global__ void __launch_bounds__(kBlock) k_recount_candidates(GraphView g, uint64_t thr, uint64_t lo, uint64_t hi,
-                                                               uint64_t w_lo, uint64_t w_hi, uint64_t *list,
-                                                               uint64_t cap, unsigned long long *counts) {
-    const int lane = threadIdx.x & 63;
-    const uint64_t nw = (g.D + 63) / 64;
-    const uint64_t wstride = ((uint64_t)gridDim.x * blockDim.x) >> 6;
-    unsigned long long nvalid = 0, ntips = 0;
-    __shared__ uint64_t wbuf[kBlock / 64][128];
-    WaveList wl{wbuf[threadIdx.x >> 6], list, counts + 2, cap};
-    for (uint64_t wb = w_lo + (((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6); wb < w_hi; wb += kScanU * wstride) {
-        uint64_t sv[kScanU], oi[kScanU], ii[kScanU];
-        WordPair a[kScanU], b[kScanU];
-        uint32_t mu[kScanU];
-#pragma unroll
-        for (int u = 0; u < kScanU; ++u) {
-            const uint64_t w = wb + u * wstride, e = w * 64 + lane;
-            const bool in = e < g.D && w < w_hi;
-            sv[u] = w < w_hi ? g.valid[w] : 0;
-            oi[u] = in ? g.out_info[e] : 0;
-            const bool cr = in && e >= lo && e < hi && ((sv[u] >> lane) & 1);
-            ii[u] = cr ? g.in_info[e] : 0;
-            mu[u] = cr ? g.mult[e] : 0;
-        }
-#pragma unroll
-        for (int u = 0; u < kScanU; ++u) {
-            a[u] = word_pair(g.valid, oi[u] & kIdxMask, nw);
-            b[u] = word_pair(g.valid, ii[u] & kIdxMask, nw);
-        }
-#pragma unroll
-        for (int u = 0; u < kScanU; ++u) {
-            const uint64_t w = wb + u * wstride, e = w * 64 + lane;
-            const bool v = (sv[u] >> lane) & 1;
-            const uint32_t cnt = __popc((unsigned)(oi[u] >> kIdxBits) & 0xF);
-            const bool t = v && (bits16(a[u].a, a[u].b, oi[u] & kIdxMask) & ((1u << cnt) - 1)) == 0;
-            const unsigned long long tm = __ballot(t);
-            if (lane == 0 && w < w_hi) {
-                ntips += __popcll(tm);
-                nvalid += __popcll(sv[u]);
-            }
-            const uint64_t l = ii[u] & kIdxMask;
-            const uint32_t in = bits16(b[u].a, b[u].b, l) & (uint32_t)((ii[u] >> kIdxBits) & 0xFFFF);  // valid in-edges
-            // _IncomingNotEqualToCurrentNode: e must not be one of its own in-edges
-            const bool self = e >= l && e - l < 16 && ((in >> (e - l)) & 1);
-            const bool c = v && e >= lo && e < hi && (uint64_t)mu[u] > thr && __popc(in) >= 2 && !self;
-            wl.push(c, e);
-        }
-    }
-    wl.finish();
-    block_add(counts, nvalid);
-    block_add(counts + 1, ntips);
-}
-
 
 
 // super rulers: chain heads and 1 in 64 of the other rulers (a ruler reached from another
@@ -979,12 +866,7 @@ __global__ void __launch_bounds__(kBlock) k_dls_lanes(GraphView g, const uint64_
 // six workgroups and 240 searches per CU (round 5: 16 x 256 / 128, 96 per CU). C5 DLS 41.6 ->
 // 34.1 ms, C3 2.9 -> 2.5 (`profiles/r06_c5_dls_lanes_ab.txt`: 32 x 128 / 64 39.1, 40 x 128 / 32
 // 36.3, 48 x 128 / 16 34.8, 64 x 64 / 32 51.9).
-#ifndef MCAAT_DLS_LANES
-#define MCAAT_DLS_LANES 40
-#define MCAAT_DLS_VIS 128
-#define MCAAT_DLS_STK 16
-#endif
-constexpr int kLdsLanes = MCAAT_DLS_LANES, kLdsVis = MCAAT_DLS_VIS, kLdsStk = MCAAT_DLS_STK;
+constexpr int kLdsLanes = 40, kLdsVis = 128, kLdsStk = 16;
 __global__ void __launch_bounds__(64) k_dls_lds(GraphView g, const uint64_t *cand, uint64_t n, int limit, int8_t *res,
                                                 uint32_t vmax, uint32_t smax) {
     __shared__ uint32_t vis_s[kLdsLanes][kLdsVis];
@@ -1301,18 +1183,16 @@ struct FcThread {
     }
 };
 
-// A/B knob: minimum waves per SIMD (6 or 8 force 80 / 64 VGPRs with spills; measured no
-// faster at C3: the kernel's time is its longest search, not its occupancy)
-#ifndef MCAAT_FC_MINW
-#define MCAAT_FC_MINW 1
-#endif
+// minimum waves per SIMD (6 or 8 force 80 / 64 VGPRs with spills; measured no faster at C3 or
+// C5, DESIGN.md §4: the kernel's time is its longest search, not its occupancy)
+constexpr int kFcMinWaves = 1;
 // One search per workgroup of one wave: the search itself is sequential (lane 0); the other
 // lanes clear its lock table first. Its path and frames live in LDS (fc_lds_bytes), so every
 // step touches global memory only for the graph, the visited bits, the lock table and the
 // frames' out_info words.
 // (Per-step latency, not occupancy, bounds this kernel: at C3 ~1.5K steps per search, each a
 // chain of dependent loads.)
-__global__ void __launch_bounds__(64, MCAAT_FC_MINW) k_findcycle(GraphView g, const uint64_t *visited, const uint64_t *starts,
+__global__ void __launch_bounds__(64, kFcMinWaves) k_findcycle(GraphView g, const uint64_t *visited, const uint64_t *starts,
                                                   uint64_t n, FcCaps caps, FcParams prm, uint64_t *sbase,
                                                   FcStatus *stat) {
     extern __shared__ __attribute__((aligned(16))) unsigned char fc_lds[];
@@ -1667,17 +1547,44 @@ unsigned long long read_counter(mcaat_ctx *ctx, unsigned long long *d) {
     return h;
 }
 
-// ids i in [0, n) with flags[i] != 0, in ascending order; returns the count
-uint64_t select_flagged(mcaat_ctx *ctx, const uint8_t *flags, uint64_t n, uint64_t *out, unsigned long long *d_num) {
-    hipcub::CountingInputIterator<uint64_t> it(0);
-    size_t tmp = 0;
-    HIP_OK(hipcub::DeviceSelect::Flagged(nullptr, tmp, it, flags, out, d_num, (size_t)n, ctx->stream));
-    DevBuf<uint8_t> t(tmp);
-    HIP_OK(hipcub::DeviceSelect::Flagged(t.p, tmp, it, flags, out, d_num, (size_t)n, ctx->stream));
-    return read_counter(ctx, d_num);
+bool verbose() {
+    static const bool v = getenv("MCAAT_VERBOSE") && getenv("MCAAT_VERBOSE")[0] == '1';
+    return v;
 }
 
+// a hipcub device call: once for the size of its temporary storage, once with the storage
+template <class F>
+void with_cub_temp(F &&call) {
+    size_t tmp = 0;
+    HIP_OK(call((void *)nullptr, tmp));
+    DevBuf<uint8_t> t(tmp);
+    HIP_OK(call((void *)t.p, tmp));
+}
 
+// the in[i] with flags[i] != 0, i in [0, n), in order, into out; returns their count
+template <class T>
+uint64_t select_flagged(mcaat_ctx *ctx, const T *in, const uint8_t *flags, uint64_t n, T *out) {
+    DevBuf<unsigned long long> num(1);
+    with_cub_temp([&](void *t, size_t &tmp) {
+        return hipcub::DeviceSelect::Flagged(t, tmp, in, flags, out, num.p, (size_t)n, ctx->stream);
+    });
+    return read_counter(ctx, num.p);
+}
+
+// edge ids (bits 0..40) in ascending order, sorted on the device (the append order of a list is
+// its atomics'; C5: 3.8M candidates, 0.25 s of host sort)
+void sort_ids(mcaat_ctx *ctx, const uint64_t *in, uint64_t *out, uint64_t n) {
+    with_cub_temp([&](void *t, size_t &tmp) {
+        return hipcub::DeviceRadixSort::SortKeys(t, tmp, in, out, (size_t)n, 0, 40, ctx->stream);
+    });
+}
+
+// the entries a rank searches: entry i on rank i % N
+std::vector<uint64_t> deal_round_robin(const std::vector<uint64_t> &v, int R, int N) {
+    std::vector<uint64_t> mine;
+    for (size_t i = R; i < v.size(); i += N) mine.push_back(v[i]);
+    return mine;
+}
 
 }  // namespace
 
@@ -1694,14 +1601,12 @@ struct PeelState {
     uint64_t slots = 0;
 };
 
-static void run_peel_rulers(mcaat_graph *g, const uint64_t *seed_bm, PeelState *pre = nullptr) {
+static void run_peel_rulers(mcaat_graph *g, const uint64_t *seed_bm, PeelState &ps) {
     mcaat_ctx *ctx = g->ctx;
     hipStream_t st = ctx->stream;
     const uint64_t D = g->D;
     if (!D) return;
     GraphView v = g->view();
-    PeelState local;
-    PeelState &ps = pre ? *pre : local;
     if (!ps.wpre) ps.slots = D;
     const uint64_t S = std::max<uint64_t>(ps.slots, 1);
     DevBuf<uint32_t> owner(S);
@@ -1713,10 +1618,7 @@ static void run_peel_rulers(mcaat_graph *g, const uint64_t *seed_bm, PeelState *
     // identity slots: the graph's filtered bitmap tells prep which edges are valid
     PeelArrays pa{ps.nf.p, ps.nxk.p, owner.p, nullptr, nullptr, seed_bm,
                   ps.wpre ? ps.post : (const uint64_t *)g->valid.p, ps.wpre, g->n_words()};
-    if (!ps.ready) {
-        hipLaunchKernelGGL(k_peel_init, dim3(grid_for(D, kBlock)), dim3(kBlock), 0, st, v, pa);
-        LAUNCH_OK();
-    }
+    if (!ps.ready) launch_at(st, dim3(grid_for(D, kBlock)), dim3(kBlock), k_peel_init, v, pa);
     // 1 in (ruler_mask + 1) unary nodes is a ruler besides the chain heads: a walk costs one
     // random read per node whatever the spacing; the rulers are then ranked one level up
     // (1 in 64 of them, plus the heads, are super rulers) before pointer jumping
@@ -1736,9 +1638,8 @@ static void run_peel_rulers(mcaat_graph *g, const uint64_t *seed_bm, PeelState *
         HIP_OK(hipMemsetAsync(cur.p, 0, cur.bytes(), st));
         const int64_t pb = knob(ctx, "cf.prep_batch", 2);  // edges per thread in flight: C3 2 / 4 / 8 / 16 -> peel 22.8 / 23.3 / 24.3 / 26.0 ms
         auto prep = pb == 4 ? k_peel_prep<4> : pb == 8 ? k_peel_prep<8> : pb == 16 ? k_peel_prep<16> : k_peel_prep<2>;
-        hipLaunchKernelGGL(prep, dim3(grid_for(D, kBlock * kTileJ)), dim3(kBlock), 0, st, D, pa, ruler_mask, list.p,
-                           cap, cur.p, blist.p, bcap, cur.p + 1);
-        LAUNCH_OK();
+        launch_at(st, dim3(grid_for(D, kBlock * kTileJ)), dim3(kBlock), prep, D, pa, ruler_mask, list.p, cap, cur.p, blist.p,
+                  bcap, cur.p + 1);
         unsigned long long hc[2];
         HIP_OK(hipMemcpyAsync(hc, cur.p, 16, hipMemcpyDeviceToHost, st));
         HIP_OK(hipStreamSynchronize(st));
@@ -1754,13 +1655,10 @@ static void run_peel_rulers(mcaat_graph *g, const uint64_t *seed_bm, PeelState *
     pa.jump = jump.p;
     pa.sowner = sowner.p;
     if (nr) {
-        hipLaunchKernelGGL(k_peel_walk, dim3(grid_for(nr, kBlock)), dim3(kBlock), 0, st, pa, list.p, nr);
-        LAUNCH_OK();
+        launch_at(st, dim3(grid_for(nr, kBlock)), dim3(kBlock), k_peel_walk, pa, list.p, nr);
         HIP_OK(hipMemsetAsync(sowner.p, 0xFF, 4 * nr, st));
         DevBuf<uint32_t> slist(nr);
-        hipLaunchKernelGGL(k_peel_super, dim3(grid_for(nr, kBlock)), dim3(kBlock), 0, st, pa, list.p, nr, slist.p,
-                           cur.p + 2);
-        LAUNCH_OK();
+        launch_at(st, dim3(grid_for(nr, kBlock)), dim3(kBlock), k_peel_super, pa, list.p, nr, slist.p, cur.p + 2);
         const uint64_t ns = read_counter(ctx, cur.p + 2);
         int rounds = 2;
         while ((1ULL << rounds) < ns + 1) ++rounds;
@@ -1771,37 +1669,27 @@ static void run_peel_rulers(mcaat_graph *g, const uint64_t *seed_bm, PeelState *
         int hchg = 1;
         for (int r = 0; ns && r < rounds; ++r) {
             if (r >= 4) HIP_OK(hipMemsetAsync(chg.p, 0, 4, st));
-            hipLaunchKernelGGL(k_peel_jump, dim3(grid_for(ns, kBlock)), dim3(kBlock), 0, st, pa, slist.p, ns, chg.p);
-            LAUNCH_OK();
+            launch_at(st, dim3(grid_for(ns, kBlock)), dim3(kBlock), k_peel_jump, pa, slist.p, ns, chg.p);
             if (r >= 4) {
                 HIP_OK(hipMemcpyAsync(&hchg, chg.p, 4, hipMemcpyDeviceToHost, st));
                 HIP_OK(hipStreamSynchronize(st));
                 if (!hchg) break;
             }
         }
-        hipLaunchKernelGGL(k_peel_final, dim3(grid_for(nr, kBlock)), dim3(kBlock), 0, st, pa, nr);
-        LAUNCH_OK();
+        launch_at(st, dim3(grid_for(nr, kBlock)), dim3(kBlock), k_peel_final, pa, nr);
     }
     DevBuf<int> changed(1);
     for (uint64_t it = 0; nb && it < D + 1; ++it) {
         HIP_OK(hipMemsetAsync(changed.p, 0, 4, st));
-        hipLaunchKernelGGL(k_peel_branch, dim3(grid_for(nb, kBlock)), dim3(kBlock), 0, st, v, pa, blist.p, nb,
-                           changed.p);
-        LAUNCH_OK();
+        launch_at(st, dim3(grid_for(nb, kBlock)), dim3(kBlock), k_peel_branch, v, pa, blist.p, nb, changed.p);
         int h = 0;
         HIP_OK(hipMemcpyAsync(&h, changed.p, 4, hipMemcpyDeviceToHost, st));
         HIP_OK(hipStreamSynchronize(st));
         if (!h) break;
     }
     // resolution reads valid bits (dev_outgoing), so removal waits until it is complete
-    if (nb) {
-        hipLaunchKernelGGL(k_peel_apply_list, dim3(grid_for(nb, kBlock)), dim3(kBlock), 0, st, v, pa, blist.p, nb);
-        LAUNCH_OK();
-    }
-    if (nr) {
-        hipLaunchKernelGGL(k_peel_apply_rulers, dim3(grid_for(nr, kBlock)), dim3(kBlock), 0, st, v, pa, list.p, nr);
-        LAUNCH_OK();
-    }
+    if (nb) launch_at(st, dim3(grid_for(nb, kBlock)), dim3(kBlock), k_peel_apply_list, v, pa, blist.p, nb);
+    if (nr) launch_at(st, dim3(grid_for(nr, kBlock)), dim3(kBlock), k_peel_apply_rulers, v, pa, list.p, nr);
     HIP_OK(hipStreamSynchronize(st));
 }
 
@@ -1809,7 +1697,7 @@ static void run_peel_rulers(mcaat_graph *g, const uint64_t *seed_bm, PeelState *
 // removed) with a per-thread step budget; if chains are longer than that, the pending
 // frontier seeds the parallel ruler/list-ranking peel, whose fixpoint from this state is
 // the same (every pending node is valid, has no valid successor and must be removed).
-static void run_peel(mcaat_graph *g, const uint64_t *seed_bm, PeelState *pre = nullptr) {
+static void run_peel(mcaat_graph *g, const uint64_t *seed_bm, PeelState &ps) {
     mcaat_ctx *ctx = g->ctx;
     // C3: the reduction walks chains of tens of thousands of edges back from a few hundred
     // seeds (budget 512: 164 walks still pending; 32768: 12, at 0.5 s), so by default the
@@ -1817,7 +1705,7 @@ static void run_peel(mcaat_graph *g, const uint64_t *seed_bm, PeelState *pre = n
     // counter-driven walks with that step budget first
     const int64_t walk_budget = knob(ctx, "cf.walk_budget", 0);
     if (walk_budget <= 0) {
-        run_peel_rulers(g, seed_bm, pre);
+        run_peel_rulers(g, seed_bm, ps);
         return;
     }
     const uint32_t kBudget = (uint32_t)std::min<int64_t>(walk_budget, 0xFFFFFFFFLL);
@@ -1829,28 +1717,24 @@ static void run_peel(mcaat_graph *g, const uint64_t *seed_bm, PeelState *pre = n
     DevBuf<uint32_t> rem(D);
     DevBuf<uint64_t> fa(D), fb(D), pend(D);
     HIP_OK(hipMemsetAsync(cur.p, 0, 16, st));
-    hipLaunchKernelGGL(k_kahn_init, dim3(grid_for(nw * 64, kBlock)), dim3(kBlock), 0, st, v, seed_bm, rem.p, fa.p,
-                       cur.p);
-    LAUNCH_OK();
+    launch_at(st, dim3(grid_for(nw * 64, kBlock)), dim3(kBlock), k_kahn_init, v, seed_bm, rem.p, fa.p, cur.p);
     uint64_t n = read_counter(ctx, cur.p);
-    static const bool verbose = getenv("MCAAT_VERBOSE") && getenv("MCAAT_VERBOSE")[0] == '1';
     while (n) {
-        if (verbose) fprintf(stderr, "[mcaat] peel: kahn frontier %llu\n", (unsigned long long)n);
+        if (verbose()) fprintf(stderr, "[mcaat] peel: kahn frontier %llu\n", (unsigned long long)n);
         HIP_OK(hipMemsetAsync(cur.p, 0, 8, st));
-        hipLaunchKernelGGL(k_kahn_walk, dim3(grid_for(n, 64)), dim3(64), 0, st, v, rem.p, fa.p, n, fb.p, cur.p,
-                           kBudget, pend.p, cur.p + 1);
-        LAUNCH_OK();
+        launch_at(st, dim3(grid_for(n, 64)), dim3(64), k_kahn_walk, v, rem.p, fa.p, n, fb.p, cur.p, kBudget, pend.p,
+                  cur.p + 1);
         n = read_counter(ctx, cur.p);
         std::swap(fa, fb);
     }
     const uint64_t np = read_counter(ctx, cur.p + 1);
-    if (verbose) fprintf(stderr, "[mcaat] peel: pending after kahn walks %llu\n", (unsigned long long)np);
+    if (verbose()) fprintf(stderr, "[mcaat] peel: pending after kahn walks %llu\n", (unsigned long long)np);
     if (np) {
         DevBuf<uint64_t> bm(nw);
         HIP_OK(hipMemsetAsync(bm.p, 0, bm.bytes(), st));
-        hipLaunchKernelGGL(k_ids_to_bits, dim3(grid_for(np, kBlock)), dim3(kBlock), 0, st, pend.p, np, bm.p);
-        LAUNCH_OK();
-        run_peel_rulers(g, bm.p);
+        launch_at(st, dim3(grid_for(np, kBlock)), dim3(kBlock), k_ids_to_bits, pend.p, np, bm.p);
+        PeelState own;  // no first pass done, one slot per edge
+        run_peel_rulers(g, bm.p, own);
     }
     HIP_OK(hipStreamSynchronize(st));
 }
@@ -1884,14 +1768,12 @@ static std::vector<uint64_t> run_dls(mcaat_graph *g, const std::vector<uint64_t>
             // per wave keep more loads in flight (C5, 3.8M candidates: 4 / 16 / 64 lanes ->
             // DLS 91 / 60 / 69 ms; C3 2.7-3.0 ms for any)
             const int lanes = (int)std::max<int64_t>(1, std::min<int64_t>(64, knob(ctx, "cf.dls_lanes", 16)));
-            hipLaunchKernelGGL(k_dls, dim3(grid_for(n, (unsigned)lanes)), dim3(64), 0, st, g->view(), dids.p, n, limit,
-                               dstk.p, cs, dvis.p, cv, dres.p, lanes);
-            LAUNCH_OK();
+            launch_at(st, dim3(grid_for(n, (unsigned)lanes)), dim3(64), k_dls, g->view(), dids.p, n, limit, dstk.p, cs,
+                      dvis.p, cv, dres.p, lanes);
             std::vector<int8_t> h(n);
             HIP_OK(hipMemcpyAsync(h.data(), dres.p, n, hipMemcpyDeviceToHost, st));
             HIP_OK(hipStreamSynchronize(st));
-            static const bool verbose = getenv("MCAAT_VERBOSE") && getenv("MCAAT_VERBOSE")[0] == '1';
-            if (verbose) {
+            if (verbose()) {
                 uint64_t over = 0, found = 0;
                 for (int8_t x : h) over += x < 0, found += x > 0;
                 fprintf(stderr, "[mcaat] dls: batch of %llu (stack %u, visited %u): found %llu, overflow %llu\n",
@@ -1936,17 +1818,6 @@ __global__ void __launch_bounds__(kBlock) k_res_pass(const int8_t *res, uint64_t
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) f[i] = res[i] == 1;
 }
 
-template <class T>
-static uint64_t select_dev(mcaat_ctx *ctx, const T *in, const uint8_t *flags, uint64_t n, T *out) {
-    hipStream_t st = ctx->stream;
-    DevBuf<unsigned long long> num(1);
-    size_t tmp = 0;
-    HIP_OK(hipcub::DeviceSelect::Flagged(nullptr, tmp, in, flags, out, num.p, (size_t)n, st));
-    DevBuf<uint8_t> t(tmp);
-    HIP_OK(hipcub::DeviceSelect::Flagged(t.p, tmp, in, flags, out, num.p, (size_t)n, st));
-    return read_counter(ctx, num.p);
-}
-
 // DepthLevelSearch over candidates already on the device (ascending ids; one GPU): the same
 // searches, batches and x8 scratch regrowth as run_dls, with the overflowed candidates and the
 // passing ids selected on the device, so only the passing ids cross to the host (C5: 3.8M
@@ -1971,8 +1842,14 @@ static std::vector<uint64_t> run_dls_dev(mcaat_graph *g, const uint64_t *dcand, 
     DevBuf<int8_t> res(n);
     DevBuf<uint64_t> idx(n), idx2(n), ids(n);
     DevBuf<uint8_t> flags(n);
-    hipLaunchKernelGGL(k_iota, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, st, idx.p, n);
-    LAUNCH_OK();
+    launch_at(st, dim3(grid_for(n, kBlock)), dim3(kBlock), k_iota, idx.p, n);
+    // the results r of the nt searches listed in idx go to res; idx becomes the overflowed ones
+    auto take_results = [&](const DevBuf<int8_t> &r, uint64_t nt) {
+        launch_at(st, dim3(grid_for(nt, kBlock)), dim3(kBlock), k_scatter_res, r.p, idx.p, nt, res.p, flags.p);
+        const uint64_t again = select_flagged(ctx, (const uint64_t *)idx.p, flags.p, nt, idx2.p);
+        std::swap(idx, idx2);
+        return again;
+    };
     uint64_t nt = n;
     bool first = true;
     // (round 5) first pass in LDS (cf.dls_lds, default 1, graphs below 2^32 - 1 edges); what
@@ -1981,14 +1858,9 @@ static std::vector<uint64_t> run_dls_dev(mcaat_graph *g, const uint64_t *dcand, 
         DevBuf<int8_t> r(n);
         // cf.dls_lds_cap (tests): fewer visited / stack entries, so searches overflow to the re-run
         const uint32_t lc = (uint32_t)std::max<int64_t>(1, knob(ctx, "cf.dls_lds_cap", kLdsVis));
-        hipLaunchKernelGGL(k_dls_lds, dim3((unsigned)((n + kLdsLanes - 1) / kLdsLanes)), dim3(64), 0, st, g->view(), dcand,
-                           n, limit, r.p, std::min<uint32_t>(lc, kLdsVis / 4 * 3), std::min<uint32_t>(lc, kLdsStk));
-        LAUNCH_OK();
-        hipLaunchKernelGGL(k_scatter_res, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, st, (const int8_t *)r.p,
-                           (const uint64_t *)idx.p, n, res.p, flags.p);
-        LAUNCH_OK();
-        nt = select_dev(ctx, (const uint64_t *)idx.p, flags.p, n, idx2.p);
-        std::swap(idx, idx2);
+        launch_at(st, dim3((unsigned)((n + kLdsLanes - 1) / kLdsLanes)), dim3(64), k_dls_lds, g->view(), dcand, n, limit,
+                  r.p, std::min<uint32_t>(lc, kLdsVis / 4 * 3), std::min<uint32_t>(lc, kLdsStk));
+        nt = take_results(r, n);
         first = false;
         cs = std::max<uint32_t>(cs, 8 * kLdsStk);
         cv = std::max<uint32_t>(cv, 8 * kLdsVis);
@@ -1998,9 +1870,7 @@ static std::vector<uint64_t> run_dls_dev(mcaat_graph *g, const uint64_t *dcand, 
         const uint64_t batch_cap = std::max<uint64_t>(64, budget / (8ULL * (cs + cv)));
         const uint64_t *src = dcand;
         if (!first) {  // the candidates to search again, in candidate order
-            hipLaunchKernelGGL(k_gather_ids, dim3(grid_for(nt, kBlock)), dim3(kBlock), 0, st, dcand,
-                               (const uint64_t *)idx.p, nt, ids.p);
-            LAUNCH_OK();
+            launch_at(st, dim3(grid_for(nt, kBlock)), dim3(kBlock), k_gather_ids, dcand, idx.p, nt, ids.p);
             src = ids.p;
         }
         DevBuf<int8_t> r(nt);
@@ -2011,26 +1881,19 @@ static std::vector<uint64_t> run_dls_dev(mcaat_graph *g, const uint64_t *dcand, 
                 1, std::min<uint64_t>({nt, (uint64_t)ctx->n_cu * 32 * (uint64_t)lanes, batch_cap}));
             DevBuf<uint64_t> dstk(nl * cs), dvis(nl * cv);
             HIP_OK(hipMemsetAsync(dvis.p, 0, dvis.bytes(), st));
-            hipLaunchKernelGGL(k_dls_lanes, dim3(grid_for(nl, (unsigned)lanes)), dim3(64), 0, st, g->view(), src, nt,
-                               limit, dstk.p, cs, dvis.p, cv, r.p, lanes, nl);
-            LAUNCH_OK();
+            launch_at(st, dim3(grid_for(nl, (unsigned)lanes)), dim3(64), k_dls_lanes, g->view(), src, nt, limit, dstk.p, cs,
+                      dvis.p, cv, r.p, lanes, nl);
             HIP_OK(hipStreamSynchronize(st));  // the scratch is freed on scope exit
         } else {
             for (uint64_t b0 = 0; b0 < nt; b0 += batch_cap) {
                 const uint64_t m = std::min<uint64_t>(batch_cap, nt - b0);
                 DevBuf<uint64_t> dstk(m * cs), dvis(m * cv);
-                hipLaunchKernelGGL(k_dls, dim3(grid_for(m, (unsigned)lanes)), dim3(64), 0, st, g->view(), src + b0, m,
-                                   limit, dstk.p, cs, dvis.p, cv, r.p + b0, lanes);
-                LAUNCH_OK();
+                launch_at(st, dim3(grid_for(m, (unsigned)lanes)), dim3(64), k_dls, g->view(), src + b0, m, limit, dstk.p, cs,
+                          dvis.p, cv, r.p + b0, lanes);
                 HIP_OK(hipStreamSynchronize(st));  // the batch's scratch is freed on scope exit
             }
         }
-        hipLaunchKernelGGL(k_scatter_res, dim3(grid_for(nt, kBlock)), dim3(kBlock), 0, st, (const int8_t *)r.p,
-                           (const uint64_t *)idx.p, nt, res.p, flags.p);
-        LAUNCH_OK();
-        const uint64_t again = select_dev(ctx, (const uint64_t *)idx.p, flags.p, nt, idx2.p);
-        std::swap(idx, idx2);
-        nt = again;
+        nt = take_results(r, nt);
         if (nt) {
             if (cs >= (1u << 26)) throw Error(MCAAT_E_CAPACITY, "DepthLevelSearch scratch exceeded 2^26 entries");
             cs *= 8;
@@ -2038,9 +1901,8 @@ static std::vector<uint64_t> run_dls_dev(mcaat_graph *g, const uint64_t *dcand, 
         }
     }
     verbose_mark(ctx, "dls.reruns");
-    hipLaunchKernelGGL(k_res_pass, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, st, (const int8_t *)res.p, n, flags.p);
-    LAUNCH_OK();
-    const uint64_t np = select_dev(ctx, dcand, flags.p, n, ids.p);
+    launch_at(st, dim3(grid_for(n, kBlock)), dim3(kBlock), k_res_pass, res.p, n, flags.p);
+    const uint64_t np = select_flagged(ctx, dcand, flags.p, n, ids.p);
     pass.resize(np);
     if (np) d2h(ctx, pass.data(), ids.p, 8 * np);
     return pass;
@@ -2284,8 +2146,7 @@ struct FcRunner {
                 d2h(g->ctx, mine.st.data(), dstat.p, Wl * sizeof(FcStatus));
             }
             verbose_mark(g->ctx, "fc.round_kernel");
-            static const bool verbose = getenv("MCAAT_VERBOSE") && getenv("MCAAT_VERBOSE")[0] == '1';
-            if (verbose && Wl) {
+            if (verbose() && Wl) {
                 std::vector<uint64_t> ord(Wl);
                 for (uint64_t i = 0; i < Wl; ++i) ord[i] = i;
                 const size_t top = std::min<size_t>(5, ord.size());
@@ -2469,11 +2330,7 @@ static std::vector<uint64_t> gather_sorted(Comm *comm, const std::vector<uint64_
 
 std::vector<uint64_t> cf_depth_level_search(mcaat_graph *g, const std::vector<uint64_t> &cand, int limit, Comm *comm) {
     if (comm && comm->world == 1) comm = nullptr;
-    if (comm) {  // candidate i is searched on rank i % N
-        std::vector<uint64_t> mine;
-        for (size_t i = comm->rank; i < cand.size(); i += comm->world) mine.push_back(cand[i]);
-        return gather_sorted(comm, run_dls(g, mine, limit));
-    }
+    if (comm) return gather_sorted(comm, run_dls(g, deal_round_robin(cand, comm->rank, comm->world), limit));
     if (knob(g->ctx, "cf.dls_host", 0) != 0 || cand.empty()) return run_dls(g, cand, limit);
     DevBuf<uint64_t> d(cand.size());
     h2d(g->ctx, d.p, cand.data(), 8 * cand.size());
@@ -2485,6 +2342,7 @@ void cf_find_cycles(mcaat_graph *g, const mcaat_cf_params &p, const std::vector<
                     Comm *comm) {
     if (comm && comm->world == 1) comm = nullptr;
     FcRunner fr(g, p, out, comm);
+    verbose_mark(g->ctx, "cf.fc_setup");
     // with threads=1 the reference's bucket loop is one ordered sequence of starts, so the
     // speculative windows run across bucket boundaries
     fr.run_bucket(starts);
@@ -2492,104 +2350,84 @@ void cf_find_cycles(mcaat_graph *g, const mcaat_cf_params &p, const std::vector<
     out->stats[7] = fr.reruns;
 }
 
-void cycle_finder(mcaat_graph *g, const mcaat_cf_params &p, mcaat_cycles *out, Comm *comm) {
-    mcaat_ctx *ctx = g->ctx;
-    hipStream_t st = ctx->stream;
-    const uint64_t D = g->D;
-    const uint64_t nw = g->n_words();
-    GraphView v = g->view();
-    StageTimer timer(ctx);
-    if (comm && comm->world == 1) comm = nullptr;
-    const int N = comm ? comm->world : 1, R = comm ? comm->rank : 0;
+// ---------------------------- CycleFinder driver -----------------------------------
+namespace {
+// The state and the stages of cycle_finder, in the order they run. With a communicator the graph
+// is replicated: the scans are split over the ranks by 64-edge words ([R*nw/N, (R+1)*nw/N): rank
+// R's ids are whole words): the tips / filter pass's two bitmaps are all-gathered (D/8 bytes
+// each), the recount's counts summed and the candidates gathered. The peel is a global fixpoint
+// over the whole graph and runs on every rank's replica (its first pass then runs as its own
+// kernel: its arrays are 12 B per edge, too much to gather); the searches of steps 5-6 are split
+// over the ranks.
+struct CfRun {
+    mcaat_graph *g;
+    mcaat_ctx *ctx;
+    hipStream_t st;
+    Comm *comm;  // null: one GPU
+    const int N, R;
+    const uint64_t D, nw;
+    const uint64_t w_lo, w_hi;  // this rank's words
     // grid-stride scans whose per-block totals meet in one counter: a capped grid keeps that
     // counter's atomics to a few thousand
-    const unsigned wgrid = grid_for(nw * 64, kBlock, (unsigned)ctx->n_cu * 16);
-    const int64_t scan_u = knob(ctx, "cf.scan_u", kScanUDefault);  // words in flight per wave (1, 2, 4)
+    const unsigned wgrid;
+    const mcaat_cf_params &p;
+    mcaat_cycles *out;
+    // DepthLevelSearch straight from the device list (one GPU; cf.dls_host=1: through the host)
+    const bool dev_dls;
+    const int64_t scan_u;  // cf.scan_u: words in flight per wave in the scans (1, 2, 4)
+    const bool walks;      // cf.walk_budget > 0: counter-driven walks ahead of the list-ranking peel
 
-    // The scans are split over the ranks by 64-edge words ([R*nw/N, (R+1)*nw/N): rank R's ids
-    // are whole words): the tips / filter pass's two bitmaps are all-gathered (D/8 bytes each),
-    // the recount's counts summed and the candidates gathered. The peel is a global fixpoint
-    // over the whole graph and runs on every rank's replica (its first pass then runs as its
-    // own kernel: its arrays are 12 B per edge, too much to gather); the searches of steps 5-6
-    // are split over the ranks.
-    const uint64_t w_lo = nw * (uint64_t)R / (uint64_t)N, w_hi = nw * (uint64_t)(R + 1) / (uint64_t)N;
-    // 1-2. CollectTips (before the multiplicity filter) -> seeds of the reduction, and
-    // InvalidateMultiplicityOneNodes, in one pass (the filtered bits go to a second bitmap)
-    DevBuf<uint64_t> seeds(nw);
-    // the list-ranking peel (the default) gets its first pass from this one (cf.fused_init=0:
-    // its own k_peel_init)
-    PeelState ps;
-    const bool fuse = !comm && knob(ctx, "cf.walk_budget", 0) <= 0 && knob(ctx, "cf.fused_init", 1) != 0 && D;
-    // (round 4) cf.compact=1: peel arrays over compact slots of the filtered edges (default one per
-    // edge; the slots are 32-bit prefix counts, so graphs of 2^32 or more edges use one per edge)
-    // Measured (C3): compact slots 36.1 ms of peel against 23.2 with one slot per edge — the
-    // removal walks of long chains pay a binary search per edge (PeelArrays::gid) and the tips
-    // pass a prefix load per successor; C5 68.1 either way. Off by default (the memory saving
-    // stays available: C5's peel state 63 -> 12 GB).
-    // (round 6) unset, it is decided after the multiplicity filter (below): compact when the filter
-    // keeps under cf.compact_pct % (30) of a fresh graph's edges. C5 keeps 18 %: its peel state
-    // falls from 63 to 12 GB at the same peel time (68.1 ms either way); C3 keeps 59 % and stays
-    // per id (compact costs it 12 ms there)
-    bool compact = knob(ctx, "cf.compact", 0) != 0 && D && D < (1ULL << 32) && knob(ctx, "cf.walk_budget", 0) <= 0;
-    // the recount's counts and ChunkStartNodes' filter come from the tips / filter pass
-    // (cf.recount = 1: the separate post-peel pass of round 2)
-    const bool fold = knob(ctx, "cf.recount", 0) == 0;
-    const uint64_t c_lo = std::min<uint64_t>(D, 64 * w_lo), c_hi = std::min<uint64_t>(D, 64 * w_hi);
-    uint64_t ccap = std::min<uint64_t>(c_hi - c_lo, (c_hi - c_lo) / 64 + (1u << 20));
-    if (knob_set(ctx, "cf.cand_cap")) ccap = (uint64_t)std::max<int64_t>(1, knob(ctx, "cf.cand_cap", 1));  // test knob
-    DevBuf<uint64_t> clist;
-    uint64_t n_cand = 0, tips_after = 0;
-    // every edge valid (as built): the passes before the filter read no unfiltered bitmap
-    const bool fresh = g->all_valid && knob(ctx, "cf.fresh", 1) != 0;
-    // (round 4) cf.pull_flags=1: the tips pass writes each edge's predecessor flags from its own
-    // side (k_tips_filter). Measured slower, off: C3 tips 14.3 -> 15.8 ms, C5 55.2 -> 61.9 ms (the
-    // in-edge window gather and in_info read for every filter-valid edge cost more than the
-    // scattered flag bytes and the clearing pass they replace)
-    const bool pull = knob(ctx, "cf.pull_flags", 0) != 0;
-    g->all_valid = false;  // the filter and the peel clear bits from here on
-    // the filtered bitmap (whole graph); the peel's compact slots index it, so it stays unchanged
-    // until the peel is done (the graph's own copy is the one the peel clears)
-    DevBuf<uint64_t> post(mcaat_graph::bitmap_words(D));
-    DevBuf<uint32_t> wpre;
-    {
-        HIP_OK(hipMemsetAsync(post.p + nw, 0, 8, st));  // the padding word
-        DevBuf<unsigned long long> c2(4);
-        HIP_OK(hipMemsetAsync(c2.p, 0, 32, st));
+    // ---- what crosses a stage boundary: the stage that writes it -> the last one that reads it
+    DevBuf<uint64_t> seeds;       // tips before the multiplicity filter (whole graph): tips_filter -> peel
+    DevBuf<uint64_t> post;        // the filtered bitmap (whole graph), unchanged while the peel's compact
+                                  // slots index it (the peel clears the graph's own copy): tips_filter -> peel
+    DevBuf<uint32_t> wpre;        // compact slots: the set bits of post before each word: tips_filter -> peel
+    PeelState ps;                 // the peel's per-edge arrays, filled when `fuse`: tips_filter -> peel
+    bool fuse = false;            // the tips pass does the peel's first pass: tips_filter -> peel
+    DevBuf<uint64_t> clist;       // post-filter candidates, in the order of their appends: tips_filter -> recount
+    uint64_t n_cand = 0;          //   their number
+    uint64_t tips_after = 0;      // post-filter tips that are not seeds (this rank's words): tips_filter -> recount
+    std::vector<uint64_t> cand;   // the candidates still valid, ascending (several ranks, cf.dls_host): recount -> dls
+    DevBuf<uint64_t> dcand;       // the same on the device (dev_dls): recount -> dls
+    uint64_t n_dcand = 0;
+    std::vector<uint64_t> pass;   // the candidates DepthLevelSearch passed, ascending: dls -> buckets
+
+    CfRun(mcaat_graph *gr, const mcaat_cf_params &pa, mcaat_cycles *res, Comm *c)
+        : g(gr), ctx(gr->ctx), st(gr->ctx->stream), comm(c), N(c ? c->world : 1), R(c ? c->rank : 0), D(gr->D),
+          nw(gr->n_words()), w_lo(nw * (uint64_t)R / (uint64_t)N), w_hi(nw * (uint64_t)(R + 1) / (uint64_t)N),
+          wgrid(grid_for(nw * 64, kBlock, (unsigned)gr->ctx->n_cu * 16)), p(pa), out(res),
+          dev_dls(!c && knob(gr->ctx, "cf.dls_host", 0) == 0), scan_u(knob(gr->ctx, "cf.scan_u", kScanUDefault)),
+          walks(knob(gr->ctx, "cf.walk_budget", 0) > 0) {}
+
+    // bytes of each rank's words of a bitmap (the all-gathers' sizes)
+    std::vector<uint64_t> word_bytes() const {
         std::vector<uint64_t> sz(N);
         for (int r = 0; r < N; ++r) sz[r] = 8 * (nw * (uint64_t)(r + 1) / N - nw * (uint64_t)r / N);
-        // 2. InvalidateMultiplicityOneNodes: this rank's words of the filtered bitmap, gathered
-        {
-            DevBuf<uint64_t> mpost;
-            if (comm) mpost.alloc(std::max<uint64_t>(w_hi - w_lo, 1));
-            if (w_hi > w_lo) {
-                auto kern = scan_u == 1 ? k_post_filter<1> : scan_u == 4 ? k_post_filter<4> : k_post_filter<2>;
-                hipLaunchKernelGGL(kern, dim3(wgrid), dim3(kBlock), 0, st, v, w_lo, w_hi, comm ? mpost.p : post.p + w_lo,
-                                   c2.p, fresh);
-                LAUNCH_OK();
-            }
-            if (comm) {
-                HIP_OK(hipStreamSynchronize(st));
-                comm->allgatherv_dev(mpost.p, post.p, sz.data());
-            }
-        }
-        if (!knob_set(ctx, "cf.compact") && !comm && fresh && fuse && D && D < (1ULL << 32) &&
-            knob(ctx, "cf.walk_budget", 0) <= 0) {
-            unsigned long long low = 0;  // every mult <= 1 edge: on a fresh graph, the edges the filter clears
-            d2h(ctx, &low, c2.p + 1, 8);
-            const uint64_t kept = D - std::min<uint64_t>(D, low);
-            compact = kept * 100 < (uint64_t)std::max<int64_t>(0, knob(ctx, "cf.compact_pct", 30)) * D;
-        }
-        if (compact) {  // compact slots: exclusive prefix of the filtered words' popcounts
+        return sz;
+    }
+
+    // 1-2. CollectTips (before the multiplicity filter) -> seeds of the reduction, and
+    // InvalidateMultiplicityOneNodes (the filtered bits go to a second bitmap), with the peel's
+    // first pass, the recount's tips and ChunkStartNodes' candidate filter
+    void tips_filter() {
+        // the list-ranking peel gets its first pass from this one (cf.fused_init=0, several ranks
+        // or walks ahead of it: its own k_peel_init)
+        fuse = !comm && !walks && knob(ctx, "cf.fused_init", 1) != 0 && D;
+        // every edge valid (as built): the passes before the filter read no unfiltered bitmap
+        const bool fresh = g->all_valid && knob(ctx, "cf.fresh", 1) != 0;
+        g->all_valid = false;  // the filter and the peel clear bits from here on
+        seeds.alloc(nw);
+        post.alloc(mcaat_graph::bitmap_words(D));
+        DevBuf<unsigned long long> cnt(4);  // [1] post_filter: mult <= 1 edges; [0], [2], [3] tips_pass
+        post_filter(fresh, cnt.p);
+        if (compact_slots(fresh, cnt.p)) {  // exclusive prefix of the filtered words' popcounts
             DevBuf<uint32_t> pc(nw + 1);
             wpre.alloc(nw + 1);
             HIP_OK(hipMemsetAsync(pc.p + nw, 0, 4, st));
-            hipLaunchKernelGGL(k_word_pop, dim3(grid_for(nw, kBlock, (unsigned)ctx->n_cu * 16)), dim3(kBlock), 0, st,
-                               (const uint64_t *)post.p, nw, pc.p);
-            LAUNCH_OK();
-            size_t tmp = 0;
-            HIP_OK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, pc.p, wpre.p, (size_t)(nw + 1), st));
-            DevBuf<uint8_t> t(tmp);
-            HIP_OK(hipcub::DeviceScan::ExclusiveSum(t.p, tmp, pc.p, wpre.p, (size_t)(nw + 1), st));
+            launch_at(st, dim3(grid_for(nw, kBlock, (unsigned)ctx->n_cu * 16)), dim3(kBlock), k_word_pop, post.p, nw, pc.p);
+            with_cub_temp([&](void *t, size_t &tmp) {
+                return hipcub::DeviceScan::ExclusiveSum(t, tmp, pc.p, wpre.p, (size_t)(nw + 1), st);
+            });
             uint32_t slots = 0;
             d2h(ctx, &slots, wpre.p + nw, 4);
             ps.post = post.p;
@@ -2597,47 +2435,28 @@ void cycle_finder(mcaat_graph *g, const mcaat_cf_params &p, mcaat_cycles *out, C
             ps.slots = slots;
         }
         if (fuse) {
-            const uint64_t S = std::max<uint64_t>(compact ? ps.slots : D, 1);
+            const uint64_t S = std::max<uint64_t>(ps.wpre ? ps.slots : D, 1);
             ps.nf.alloc(4 * S);
             ps.nxk.alloc(S);
-            if (!pull) HIP_OK(hipMemsetAsync(ps.nf.p, 0, ps.nf.bytes(), st));  // pull: every slot read is written
+            HIP_OK(hipMemsetAsync(ps.nf.p, 0, ps.nf.bytes(), st));  // the flag bytes other nodes set
             ps.ready = true;
         }
-        // 1. CollectTips (before the filter: the seeds of the reduction), with the peel's first
-        // pass and the candidate filter
-        PeelArrays fa{fuse ? ps.nf.p : nullptr, fuse ? ps.nxk.p : nullptr, nullptr, nullptr, nullptr, nullptr,
-                      post.p, compact ? wpre.p : nullptr, nw};
-      for (;;) {
-        if (fold) clist.alloc(ccap ? ccap : 1);
-        HIP_OK(hipMemsetAsync(c2.p, 0, 8, st));
-        HIP_OK(hipMemsetAsync(c2.p + 2, 0, 16, st));
+        const uint64_t c_lo = std::min<uint64_t>(D, 64 * w_lo), c_hi = std::min<uint64_t>(D, 64 * w_hi);
+        uint64_t ccap = std::min<uint64_t>(c_hi - c_lo, (c_hi - c_lo) / 64 + (1u << 20));
+        if (knob_set(ctx, "cf.cand_cap")) ccap = (uint64_t)std::max<int64_t>(1, knob(ctx, "cf.cand_cap", 1));  // test knob
         DevBuf<uint64_t> mseeds;  // this rank's words when the bitmap is gathered
         if (comm) mseeds.alloc(std::max<uint64_t>(w_hi - w_lo, 1));
-        if (w_hi > w_lo) {
-            auto pick = [&](auto su) {
-                constexpr int U = decltype(su)::value;
-                return fresh ? (pull ? k_tips_filter<U, true, true> : k_tips_filter<U, true, false>)
-                             : (pull ? k_tips_filter<U, false, true> : k_tips_filter<U, false, false>);
-            };
-            auto kern = scan_u == 1 ? pick(std::integral_constant<int, 1>{})
-                        : scan_u == 4 ? pick(std::integral_constant<int, 4>{}) : pick(std::integral_constant<int, 2>{});
-            hipLaunchKernelGGL(kern, dim3(wgrid), dim3(kBlock), 0, st, v, w_lo, w_hi, comm ? mseeds.p : seeds.p + w_lo,
-                               (const uint64_t *)post.p, c2.p, fa, (uint64_t)p.threshold_multiplicity,
-                               fold ? clist.p : (uint64_t *)nullptr, ccap);
-            LAUNCH_OK();
-        }
         unsigned long long hc[4];
-        HIP_OK(hipMemcpyAsync(hc, c2.p, 32, hipMemcpyDeviceToHost, st));
-        HIP_OK(hipStreamSynchronize(st));
-        if (fold && hc[3] > ccap) {  // more candidates than the list held: the pass again (idempotent), sized
+        tips_pass(fresh, cnt.p, comm ? mseeds.p : seeds.p + w_lo, ccap, hc);
+        while (hc[3] > ccap) {  // more candidates than the list held: the pass again (idempotent), sized
             ccap = hc[3];
-            if (fuse && !pull) HIP_OK(hipMemsetAsync(ps.nf.p, 0, ps.nf.bytes(), st));  // its flag bytes are set again
-            continue;
+            if (fuse) HIP_OK(hipMemsetAsync(ps.nf.p, 0, ps.nf.bytes(), st));  // its flag bytes are set again
+            tips_pass(fresh, cnt.p, comm ? mseeds.p : seeds.p + w_lo, ccap, hc);
         }
-        n_cand = fold ? hc[3] : 0;
+        n_cand = hc[3];
         tips_after = hc[2];
         if (comm) {
-            comm->allgatherv_dev(mseeds.p, seeds.p, sz.data());
+            comm->allgatherv_dev(mseeds.p, seeds.p, word_bytes().data());
             const auto all = comm->allgather_vec(std::vector<unsigned long long>{hc[0], hc[1]});
             hc[0] = hc[1] = 0;
             for (int r = 0; r < N; ++r) hc[0] += all[2 * r], hc[1] += all[2 * r + 1];
@@ -2646,163 +2465,169 @@ void cycle_finder(mcaat_graph *g, const mcaat_cf_params &p, mcaat_cycles *out, C
         out->stats[1] = hc[1];
         // the graph's bitmap becomes the filtered one (its pre-filter bits are no longer read)
         HIP_OK(hipMemcpyAsync(g->valid.p, post.p, 8 * nw, hipMemcpyDeviceToDevice, st));
-        v = g->view();
-        break;
-      }
     }
-    timer.mark("tips_filter");
-    verbose_mark(ctx, "cf.tips_filter");
+
+    // 2. InvalidateMultiplicityOneNodes: this rank's words of the filtered bitmap, gathered
+    void post_filter(bool fresh, unsigned long long *cnt) {
+        HIP_OK(hipMemsetAsync(post.p + nw, 0, 8, st));  // the padding word
+        HIP_OK(hipMemsetAsync(cnt, 0, 32, st));
+        DevBuf<uint64_t> mpost;
+        if (comm) mpost.alloc(std::max<uint64_t>(w_hi - w_lo, 1));
+        if (w_hi > w_lo) {
+            auto kern = scan_u == 1 ? k_post_filter<1> : scan_u == 4 ? k_post_filter<4> : k_post_filter<2>;
+            launch_at(st, dim3(wgrid), dim3(kBlock), kern, g->view(), w_lo, w_hi, comm ? mpost.p : post.p + w_lo, cnt, fresh);
+        }
+        if (comm) {
+            HIP_OK(hipStreamSynchronize(st));
+            comm->allgatherv_dev(mpost.p, post.p, word_bytes().data());
+        }
+    }
+
+    // whether the peel's arrays hold compact slots of the filtered edges instead of one per edge
+    // (the slots are 32-bit prefix counts, so graphs of 2^32 or more edges use one per edge).
+    // Measured (C3): compact slots 36.1 ms of peel against 23.2 with one slot per edge — the
+    // removal walks of long chains pay a binary search per edge (PeelArrays::gid) and the tips
+    // pass a prefix load per successor; C5 68.1 either way, its peel state 63 -> 12 GB.
+    // (round 6) cf.compact unset: compact when the filter keeps under cf.compact_pct % (30) of a
+    // fresh graph's edges. C5 keeps 18 %; C3 keeps 59 % and stays per id
+    bool compact_slots(bool fresh, const unsigned long long *cnt) {
+        if (!D || D >= (1ULL << 32) || walks) return false;
+        if (knob_set(ctx, "cf.compact")) return knob(ctx, "cf.compact", 0) != 0;
+        if (!fresh || !fuse) return false;
+        unsigned long long low = 0;  // every mult <= 1 edge: on a fresh graph, the edges the filter clears
+        d2h(ctx, &low, cnt + 1, 8);
+        const uint64_t kept = D - std::min<uint64_t>(D, low);
+        return kept * 100 < (uint64_t)std::max<int64_t>(0, knob(ctx, "cf.compact_pct", 30)) * D;
+    }
+
+    // 1. CollectTips (before the filter: the seeds of the reduction) into this rank's words of the
+    // seeds, with the peel's first pass and the candidate filter into clist (ccap entries); hc:
+    // the pass's counters (k_tips_filter)
+    void tips_pass(bool fresh, unsigned long long *cnt, uint64_t *my_seeds, uint64_t ccap, unsigned long long *hc) {
+        clist.alloc(ccap ? ccap : 1);
+        HIP_OK(hipMemsetAsync(cnt, 0, 8, st));
+        HIP_OK(hipMemsetAsync(cnt + 2, 0, 16, st));
+        const PeelArrays fa{fuse ? ps.nf.p : nullptr, fuse ? ps.nxk.p : nullptr, nullptr, nullptr, nullptr, nullptr,
+                            post.p, ps.wpre, nw};
+        if (w_hi > w_lo) {
+            auto kern = scan_u == 1   ? (fresh ? k_tips_filter<1, true> : k_tips_filter<1, false>)
+                        : scan_u == 4 ? (fresh ? k_tips_filter<4, true> : k_tips_filter<4, false>)
+                                      : (fresh ? k_tips_filter<2, true> : k_tips_filter<2, false>);
+            launch_at(st, dim3(wgrid), dim3(kBlock), kern, g->view(), w_lo, w_hi, my_seeds, post.p, cnt, fa,
+                      (uint64_t)p.threshold_multiplicity, clist.p, ccap);
+        }
+        HIP_OK(hipMemcpyAsync(hc, cnt, 32, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+    }
+
     // 3. RecursiveReduction from every seed
-    if (!fuse) ps.ready = false;
-    run_peel(g, seeds.p, (fuse || compact) ? &ps : nullptr);
-    seeds.release();
-    ps.nf.release();
-    ps.nxk.release();
-    post.release();
-    wpre.release();
-    timer.mark("peel");
-    verbose_mark(ctx, "cf.peel");
+    void peel() {
+        run_peel(g, seeds.p, ps);
+        seeds.release();
+        ps.nf.release();
+        ps.nxk.release();
+        post.release();
+        wpre.release();
+    }
+
     // 4-5. valid count + tips after pruning, and ChunkStartNodes' candidate filter (its
     // InvalidateMultiplicityOneNodes, cycle_finder.cpp:391-393, is a no-op here: step 2 already
     // cleared every mult <= 1 edge and nothing since sets a valid bit, and the count it would
-    // print is stats[1], every mult <= 1 edge, valid or not)
-    std::vector<uint64_t> cand;
-    DevBuf<uint64_t> dcand;  // one GPU, fold path: the sorted candidates stay on the device
-    uint64_t n_dcand = 0;
-    const bool dev_dls = knob(ctx, "cf.dls_host", 0) == 0;
-    if (fold) {
-        // valid count: a popcount of this rank's words; tips: the post-filter tips that were
-        // not seeds (tips pass); candidates: the listed ones still valid, in ascending id order
+    // print is stats[1], every mult <= 1 edge, valid or not).
+    // valid count: a popcount of this rank's words; tips: the post-filter tips that were not
+    // seeds (tips pass); candidates: the listed ones still valid, in ascending id order
+    void recount() {
         DevBuf<unsigned long long> c1(1);
         HIP_OK(hipMemsetAsync(c1.p, 0, 8, st));
-        if (w_hi > w_lo) {
-            hipLaunchKernelGGL(k_popcount, dim3(wgrid), dim3(kBlock), 0, st, (const uint64_t *)g->valid.p, w_lo, w_hi, c1.p);
-            LAUNCH_OK();
-        }
+        if (w_hi > w_lo) launch_at(st, dim3(wgrid), dim3(kBlock), k_popcount, g->valid.p, w_lo, w_hi, c1.p);
         out->stats[2] = read_counter(ctx, c1.p);
-        out->stats[3] = tips_after;  // this rank's words (summed over the ranks below)
+        out->stats[3] = tips_after;
         if (n_cand) {
             DevBuf<uint8_t> fl(n_cand);
             DevBuf<uint64_t> kept(n_cand), sorted(n_cand);
-            DevBuf<unsigned long long> nk(1);
-            hipLaunchKernelGGL(k_still_valid, dim3(grid_for(n_cand, kBlock)), dim3(kBlock), 0, st, (const uint64_t *)g->valid.p,
-                               (const uint64_t *)clist.p, n_cand, fl.p);
-            LAUNCH_OK();
-            size_t tmp = 0;
-            HIP_OK(hipcub::DeviceSelect::Flagged(nullptr, tmp, clist.p, fl.p, kept.p, nk.p, (size_t)n_cand, st));
-            {
-                DevBuf<uint8_t> t(tmp);
-                HIP_OK(hipcub::DeviceSelect::Flagged(t.p, tmp, clist.p, fl.p, kept.p, nk.p, (size_t)n_cand, st));
-            }
-            const uint64_t nkept = read_counter(ctx, nk.p);
-            if (nkept) {
-                tmp = 0;
-                HIP_OK(hipcub::DeviceRadixSort::SortKeys(nullptr, tmp, kept.p, sorted.p, (size_t)nkept, 0, 40, st));
-                DevBuf<uint8_t> t(tmp);
-                HIP_OK(hipcub::DeviceRadixSort::SortKeys(t.p, tmp, kept.p, sorted.p, (size_t)nkept, 0, 40, st));
-            }
-            if (comm || !dev_dls) {
-                cand.resize(nkept);
-                if (nkept) d2h(ctx, cand.data(), sorted.p, 8 * nkept);
-            } else {  // one GPU: DepthLevelSearch straight from the device list
+            launch_at(st, dim3(grid_for(n_cand, kBlock)), dim3(kBlock), k_still_valid, g->valid.p, clist.p, n_cand, fl.p);
+            const uint64_t nkept = select_flagged(ctx, (const uint64_t *)clist.p, fl.p, n_cand, kept.p);
+            if (nkept) sort_ids(ctx, kept.p, sorted.p, nkept);
+            if (dev_dls) {
                 dcand = std::move(sorted);
                 n_dcand = nkept;
+            } else {
+                cand.resize(nkept);
+                if (nkept) d2h(ctx, cand.data(), sorted.p, 8 * nkept);
             }
         }
         clist.release();
-    } else {
-        // rank R takes the candidates among its words' ids, and counts over its words
-        const uint64_t lo = std::min<uint64_t>(D, 64 * w_lo), hi = std::min<uint64_t>(D, 64 * w_hi);
-        uint64_t cap = std::min<uint64_t>(hi - lo, (hi - lo) / 64 + (1u << 20));
-        if (knob_set(ctx, "cf.cand_cap")) cap = (uint64_t)std::max<int64_t>(1, knob(ctx, "cf.cand_cap", 1));  // test knob
-        DevBuf<unsigned long long> c3(3);
-        for (;;) {
-            DevBuf<uint64_t> list(cap ? cap : 1);
-            HIP_OK(hipMemsetAsync(c3.p, 0, 24, st));
-            if (w_hi > w_lo) {
-                auto kern = scan_u == 1 ? k_recount_candidates<1> : scan_u == 4 ? k_recount_candidates<4>
-                                                                                : k_recount_candidates<2>;
-                hipLaunchKernelGGL(kern, dim3(wgrid), dim3(kBlock), 0, st, v,
-                                   (uint64_t)p.threshold_multiplicity, lo, hi, w_lo, w_hi, list.p, cap, c3.p);
-                LAUNCH_OK();
-            }
-            unsigned long long hc[3];
-            HIP_OK(hipMemcpyAsync(hc, c3.p, 24, hipMemcpyDeviceToHost, st));
-            HIP_OK(hipStreamSynchronize(st));
-            out->stats[2] = hc[0];
-            out->stats[3] = hc[1];
-            if (hc[2] > cap) {  // more candidates than the first list held: the pass again, sized
-                cap = hc[2];
-                continue;
-            }
-            cand.resize(hc[2]);
-            if (hc[2]) {
-                // ascending id order (the append order is the atomics'): sorted on the device
-                // (C5: 3.8M candidates, 0.25 s of host sort)
-                DevBuf<uint64_t> sorted(hc[2]);
-                size_t tmp = 0;
-                HIP_OK(hipcub::DeviceRadixSort::SortKeys(nullptr, tmp, list.p, sorted.p, (size_t)hc[2], 0, 40, st));
-                DevBuf<uint8_t> t(tmp);
-                HIP_OK(hipcub::DeviceRadixSort::SortKeys(t.p, tmp, list.p, sorted.p, (size_t)hc[2], 0, 40, st));
-                d2h(ctx, cand.data(), sorted.p, 8 * hc[2]);
-            }
-            break;
+        if (comm) {  // the ranks' word counts summed
+            const auto all = comm->allgather_vec(std::vector<uint64_t>{out->stats[2], out->stats[3]});
+            out->stats[2] = out->stats[3] = 0;
+            for (int r = 0; r < N; ++r) out->stats[2] += all[2 * r], out->stats[3] += all[2 * r + 1];
         }
     }
-    if (comm) {  // the ranks' word counts summed
-        const auto all = comm->allgather_vec(std::vector<uint64_t>{out->stats[2], out->stats[3]});
-        out->stats[2] = out->stats[3] = 0;
-        for (int r = 0; r < N; ++r) out->stats[2] += all[2 * r], out->stats[3] += all[2 * r + 1];
+
+    // every rank's candidates
+    void gather_candidates() {
+        if (comm) cand = gather_sorted(comm, cand);
     }
+
+    // 5. ChunkStartNodes' DepthLevelSearch from every candidate (several ranks: dealt round-robin)
+    void dls() {
+        if (dev_dls) pass = run_dls_dev(g, dcand.p, n_dcand, p.cycle_max_length);
+        else pass = cf_depth_level_search(g, cand, p.cycle_max_length, comm);
+        dcand.release();
+    }
+
+    // the passing candidates by bucket (ceil(log2(multiplicity)), descending), ascending ids within one
+    void buckets() {
+        std::map<int, std::vector<uint64_t>, std::greater<int>> chunks;
+        if (!pass.empty()) {
+            DevBuf<uint64_t> ids(pass.size());
+            DevBuf<uint16_t> m(pass.size());
+            HIP_OK(hipMemcpyAsync(ids.p, pass.data(), 8 * pass.size(), hipMemcpyHostToDevice, st));
+            launch_at(st, dim3(grid_for(pass.size(), kBlock)), dim3(kBlock), k_gather_mult, g->mult.p, ids.p,
+                      (uint64_t)pass.size(), m.p);
+            std::vector<uint16_t> hm(pass.size());
+            HIP_OK(hipMemcpyAsync(hm.data(), m.p, 2 * pass.size(), hipMemcpyDeviceToHost, st));
+            HIP_OK(hipStreamSynchronize(st));
+            for (size_t i = 0; i < pass.size(); ++i) {
+                const double l2 = std::ceil(std::log2(double(hm[i])));  // cycle_finder.cpp:414
+                chunks[(int)l2].push_back(pass[i]);
+            }
+        }
+        for (auto &kv : chunks)
+            for (uint64_t id : kv.second) { out->cand_ids.push_back(id); out->cand_bucket.push_back(kv.first); }
+        out->stats[4] = out->cand_ids.size();
+    }
+
+    // 6. bucket loop
+    void find_cycle() { cf_find_cycles(g, p, out->cand_ids, out, comm); }
+};
+}  // namespace
+
+void cycle_finder(mcaat_graph *g, const mcaat_cf_params &p, mcaat_cycles *out, Comm *comm) {
+    mcaat_ctx *ctx = g->ctx;
+    StageTimer timer(ctx);
+    if (comm && comm->world == 1) comm = nullptr;
+    CfRun s(g, p, out, comm);
+    s.tips_filter();
+    timer.mark("tips_filter");
+    verbose_mark(ctx, "cf.tips_filter");
+    s.peel();
+    timer.mark("peel");
+    verbose_mark(ctx, "cf.peel");
+    s.recount();
     timer.mark("recount");
-    if (comm) cand = gather_sorted(comm, cand);
+    s.gather_candidates();
     timer.mark("candidates");
     verbose_mark(ctx, "cf.candidates");
-    std::vector<uint64_t> pass;
-    if (comm) {
-        // candidate i is searched on rank i % N
-        std::vector<uint64_t> mine;
-        for (size_t i = R; i < cand.size(); i += N) mine.push_back(cand[i]);
-        pass = gather_sorted(comm, run_dls(g, mine, p.cycle_max_length));
-    } else if (fold && dev_dls) {
-        pass = run_dls_dev(g, dcand.p, n_dcand, p.cycle_max_length);
-        dcand.release();
-    } else {
-        pass = run_dls(g, cand, p.cycle_max_length);
-    }
+    s.dls();
     timer.mark("dls");
     verbose_mark(ctx, "cf.dls");
-    std::map<int, std::vector<uint64_t>, std::greater<int>> chunks;
-    if (!pass.empty()) {
-        DevBuf<uint64_t> ids(pass.size());
-        DevBuf<uint16_t> m(pass.size());
-        HIP_OK(hipMemcpyAsync(ids.p, pass.data(), 8 * pass.size(), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_gather_mult, dim3(grid_for(pass.size(), kBlock)), dim3(kBlock), 0, st, g->mult.p, ids.p,
-                           (uint64_t)pass.size(), m.p);
-        LAUNCH_OK();
-        std::vector<uint16_t> hm(pass.size());
-        HIP_OK(hipMemcpyAsync(hm.data(), m.p, 2 * pass.size(), hipMemcpyDeviceToHost, st));
-        HIP_OK(hipStreamSynchronize(st));
-        for (size_t i = 0; i < pass.size(); ++i) {
-            const double l2 = std::ceil(std::log2(double(hm[i])));  // cycle_finder.cpp:414
-            chunks[(int)l2].push_back(pass[i]);
-        }
-    }
-    for (auto &kv : chunks)
-        for (uint64_t id : kv.second) { out->cand_ids.push_back(id); out->cand_bucket.push_back(kv.first); }
-    out->stats[4] = out->cand_ids.size();
-    // 6. bucket loop
+    s.buckets();
     verbose_mark(ctx, "cf.chunks");
-    FcRunner fr(g, p, out, comm);
-    verbose_mark(ctx, "cf.fc_setup");
-    // with threads=1 the reference's bucket loop is one ordered sequence of starts, so the
-    // speculative windows run across bucket boundaries
-    fr.run_bucket(out->cand_ids);
-    out->stats[6] = fr.rounds;
-    out->stats[7] = fr.reruns;
+    s.find_cycle();
     timer.mark("find_cycle");
     verbose_mark(ctx, "cf.find_cycle");
-    HIP_OK(hipStreamSynchronize(st));
+    HIP_OK(hipStreamSynchronize(ctx->stream));
     timer.finish();
 }
 // the valid edges in ascending id order (their rank = their position) and each one's valid

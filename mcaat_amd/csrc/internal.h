@@ -414,6 +414,14 @@ inline unsigned grid_for(uint64_t n, unsigned block, unsigned cap = 65535u * 16)
     return (unsigned)g;
 }
 
+// a kernel launch with the geometry given: the arguments converted to the kernel's parameter
+// types (a DevBuf's pointer to a pointer to const), the launch checked
+template <class... P, class... A>
+void launch_at(hipStream_t st, dim3 grid, dim3 block, void (*k)(P...), A &&...a) {
+    hipLaunchKernelGGL(k, grid, block, 0, st, static_cast<P>(a)...);
+    LAUNCH_OK();
+}
+
 inline uint64_t next_pow2(uint64_t x) {
     uint64_t p = 1;
     while (p < x) p <<= 1;

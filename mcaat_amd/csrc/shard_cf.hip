@@ -121,14 +121,7 @@ __device__ __forceinline__ uint64_t lb_range(const uint64_t *a, uint64_t lo, uin
 }
 
 // ---------------------------------------------------------------- launches
-// every launch of the file: the arguments converted to the kernel's parameter types (a DevBuf's
-// pointer to a pointer to const), the launch checked
-template <class... P, class... A>
-void launch_at(hipStream_t st, dim3 grid, dim3 block, void (*k)(P...), A &&...a) {
-    hipLaunchKernelGGL(k, grid, block, 0, st, static_cast<P>(a)...);
-    LAUNCH_OK();
-}
-
+// every launch of the file goes through launch_at (internal.h)
 struct Launch {
     hipStream_t st;
     unsigned cap;  // most blocks of a grid-stride launch (0: grid_for's own limit)

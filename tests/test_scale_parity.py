@@ -99,9 +99,6 @@ KNOBS = {
     # the ruler / branch lists and the candidate list start with one entry: the passes that
     # fill them run again with the counted sizes
     "list_regrow": {"cf.peel_list_cap": 1, "cf.cand_cap": 1},
-    # the round-2 recount pass after the peel instead of the tips-pass fold, and with regrowth
-    "recount_pass": {"cf.recount": 1},
-    "recount_pass_regrow": {"cf.recount": 1, "cf.cand_cap": 1},
     # DepthLevelSearch through the host lists, and the device driver's scratch regrowth
     "dls_host": {"cf.dls_host": 1},
     "dls_dev_regrow": {"cf.dls_stack": 1, "cf.dls_visited": 2, "cf.dls_lds": 0},
@@ -120,10 +117,6 @@ KNOBS = {
     "peel_compact_own_init": {"cf.compact": 1, "cf.fused_init": 0},
     "tips_not_fresh": {"cf.fresh": 0},
     "compact_lists_regrow": {"cf.compact": 1, "cf.peel_list_cap": 1, "cf.cand_cap": 1, "cf.fresh": 0},
-    # (round 4) predecessor flags written from each edge's own side, per-id and compact slots,
-    # fresh and with the candidate list regrown (the pass runs twice without clearing)
-    "pull_flags": {"cf.pull_flags": 1},
-    "pull_flags_compact_regrow": {"cf.pull_flags": 1, "cf.compact": 1, "cf.cand_cap": 1, "cf.fresh": 0},
     # (round 4) DepthLevelSearch with per-lane scratch instead of per-candidate batches
     "dls_persist": {"cf.dls_persist": 1},
     "dls_persist_regrow": {"cf.dls_persist": 1, "cf.dls_stack": 1, "cf.dls_visited": 2},
@@ -202,6 +195,17 @@ def test_forced_branches_really_taken(gpu_ctx):
     assert res.stats[6] > base.stats[6] and res.stats[4] == base.stats[4] > 0
     with pytest.raises(M.McaatError):
         gpu_ctx.set_knob("no.such_knob", 1)
+
+
+def test_retired_knobs_are_unknown(gpu_ctx):
+    """The CycleFinder knobs whose paths are gone answer MCAAT_E_INVALID (-1) like any unknown
+    name; a surviving knob is still accepted."""
+    for name in ("cf.pull_flags", "cf.recount"):
+        with pytest.raises(M.McaatError) as err:
+            gpu_ctx.set_knob(name, 1)
+        assert err.value.code == -1, name
+    gpu_ctx.set_knob("cf.compact", 1)
+    gpu_ctx.set_knob("cf.compact", -1)  # back to the default
 
 
 # ---- coverage-matched samples of the bench configs ----------------------------------

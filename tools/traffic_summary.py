@@ -25,7 +25,7 @@ n_bases = float(sys.argv[3]) if len(sys.argv) > 3 else 300e6 * 150  # C3
 NAMES = {"k_sk_scatter": "sk_scatter", "k_lds_count": "lds_count", "k_l2_scatter": "l2_partition",
          "k_l2_hist": "l2_hist"}
 STREAM = {"k_lds_count", "k_l2_scatter", "k_l2_hist", "k_fallback", "k_part_occ", "k_tips_filter",
-          "k_recount_candidates", "k_fq_nlcount", "k_fq_nlpos", "k_concat_parts"}
+          "k_fq_nlcount", "k_fq_nlpos", "k_concat_parts"}
 MIXED_STREAM_BYTES = {"k_sk_scatter": 0.25 * n_bases}
 fetch = collections.defaultdict(float)
 write = collections.defaultdict(float)
