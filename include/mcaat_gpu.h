@@ -381,8 +381,6 @@ void mcaat_reset_timing(mcaat_ctx *ctx);
  *   cf.dls_stack / cf.dls_visited   initial DepthLevelSearch scratch (grows x8 on overflow)
  *   cf.fc_lock / cf.fc_relax / cf.fc_out   initial FindCycle scratch (grows on overflow)
  *   cf.fc_window       initial FindCycle speculation window
- *   cf.walk_budget     > 0: counter-driven peel walks of this many steps before the
- *                      list-ranking peel (default 0: the list-ranking peel alone)
  *   cf.ruler_mask      1 in (mask + 1) unary nodes is a peel ruler besides the chain heads
  *   cf.fused_init      0: the peel's first pass as its own kernel (default 1: done by the tips /
  *                      multiplicity-filter pass)

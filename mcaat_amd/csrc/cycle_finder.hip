@@ -631,66 +631,6 @@ __global__ void __launch_bounds__(kBlock) k_peel_apply_rulers(GraphView g, PeelA
     }
 }
 
-// ---- counter-driven peel (Kahn-style) ----
-// rem[e] = number of valid successors of a valid edge. Removing a child decrements each valid
-// parent; the thread whose decrement reaches zero owns that parent, removes it and keeps
-// walking, so every parent is removed exactly when its last valid child is (the reference's
-// recursion fixpoint) and chains are walked without a kernel per level.
-__global__ void __launch_bounds__(kBlock) k_kahn_init(GraphView g, const uint64_t *seed, uint32_t *rem, uint64_t *out,
-                                                      unsigned long long *cursor) {
-    const int lane = threadIdx.x & 63;
-    const uint64_t nw = (g.D + 63) / 64;
-    const uint64_t wstride = ((uint64_t)gridDim.x * blockDim.x) >> 6;
-    for (uint64_t w = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; w < nw; w += wstride) {
-        const uint64_t e = w * 64 + lane;
-        bool f = false;
-        if (e < g.D) {
-            uint32_t od = 0;
-            if (bit_get(g.valid, e)) od = (uint32_t)dev_outdeg(g, e);
-            rem[e] = od;
-            f = od == 0 && ((seed[w] & g.valid[w]) >> lane) & 1;
-        }
-        const unsigned long long m = __ballot(f);
-        unsigned long long off = 0;
-        if (lane == 0 && m) off = atomicAdd(cursor, (unsigned long long)__popcll(m));
-        off = __shfl(off, 0);
-        if (f) out[off + __popcll(m & ((lane == 0) ? 0ull : (~0ull >> (64 - lane))))] = e;
-    }
-}
-
-__global__ void __launch_bounds__(kBlock) k_kahn_walk(GraphView g, uint32_t *rem, const uint64_t *f, uint64_t n,
-                                                      uint64_t *next, unsigned long long *cursor, uint32_t budget,
-                                                      uint64_t *pend, unsigned long long *pend_n) {
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        uint64_t t = f[i];
-        for (uint32_t step = 0;; ++step) {
-            if (step == budget) {  // long chain: leave t (counter already zero, still valid) pending
-                pend[atomicAdd(pend_n, 1ull)] = t;
-                break;
-            }
-            // parents are read before t is invalidated (valid-only in-edges of t)
-            uint64_t in[4];
-            const int ni = dev_incoming(g, t, in);
-            atomicAnd((unsigned long long *)&g.valid[t >> 6], ~(1ull << (t & 63)));
-            uint64_t cont = kNone;
-            for (int j = 0; j < ni; ++j) {
-                if (atomicSub(&rem[in[j]], 1u) != 1u) continue;
-                if (cont == kNone) cont = in[j];
-                else next[atomicAdd(cursor, 1ull)] = in[j];
-            }
-            if (cont == kNone) break;
-            t = cont;
-        }
-    }
-}
-
-__global__ void __launch_bounds__(kBlock) k_ids_to_bits(const uint64_t *ids, uint64_t n, uint64_t *bm) {
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
-        atomicOr((unsigned long long *)&bm[ids[i] >> 6], 1ull << (ids[i] & 63));
-}
-
 // ------------------------------ DLS ------------------------------------------
 // DepthLevelSearch(v, v, limit) (cycle_finder.cpp:248-343), one thread per candidate.
 // res: 1 found, 0 not found, -1 scratch overflow (re-run with larger caps)
@@ -766,87 +706,6 @@ __global__ void __launch_bounds__(kBlock) k_dls(GraphView g, const uint64_t *can
         if (v == start && depth > 1) { found = 1; break; }
     }
     res[i] = over ? -1 : found;
-}
-
-// (round 4) The same search with scratch per lane instead of per candidate: lane q of the
-// launch takes candidates q, q + L, q + 2L, ... (L lanes in all), so a wave's time is the sum of
-// its lanes' searches, not the longest search of one batch, and every candidate gets the large
-// scratch. The visited table is not cleared between searches: an entry carries its search's
-// generation in bits 56..63 (node ids are below 2^56), and entries of other generations read
-// as empty; the table is cleared when the 8-bit generation wraps.
-__device__ __forceinline__ bool gset_insert(uint64_t *tab, uint32_t cap, uint64_t x, uint64_t gen, uint32_t &size,
-                                            bool &over) {
-    const uint64_t tx = (gen << 56) | x;
-    uint32_t s = (uint32_t)(mix64(x) & (cap - 1));
-    for (;;) {
-        const uint64_t c = tab[s];
-        if (c == tx) return false;
-        if ((c >> 56) != gen) {
-            if (size + 1 > cap / 4 * 3) { over = true; return false; }
-            tab[s] = tx;
-            ++size;
-            return true;
-        }
-        s = (s + 1) & (cap - 1);
-    }
-}
-__device__ __forceinline__ bool gset_contains(const uint64_t *tab, uint32_t cap, uint64_t x, uint64_t gen) {
-    const uint64_t tx = (gen << 56) | x;
-    uint32_t s = (uint32_t)(mix64(x) & (cap - 1));
-    for (;;) {
-        const uint64_t c = tab[s];
-        if (c == tx) return true;
-        if ((c >> 56) != gen) return false;
-        s = (s + 1) & (cap - 1);
-    }
-}
-
-// vis_all zeroed by the caller (generation 0 = empty); lpw active lanes per wave
-__global__ void __launch_bounds__(kBlock) k_dls_lanes(GraphView g, const uint64_t *cand, uint64_t n, int limit,
-                                                      uint64_t *stack_all, uint32_t cs, uint64_t *vis_all, uint32_t cv,
-                                                      int8_t *res, int lpw, uint64_t n_lanes) {
-    const int lane = threadIdx.x & 63;
-    if (lane >= lpw) return;
-    const uint64_t q = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) / 64 * lpw + lane;
-    if (q >= n_lanes) return;
-    uint64_t *stk = stack_all + q * cs;
-    uint64_t *vis = vis_all + q * cv;
-    uint64_t gen = 0;
-    for (uint64_t i = q; i < n; i += n_lanes) {
-        if (++gen == 256) {
-            for (uint32_t j = 0; j < cv; ++j) vis[j] = 0;
-            gen = 1;
-        }
-        const uint64_t start = cand[i];
-        uint32_t sp = 0, vsize = 0;
-        bool over = false;
-        stk[sp++] = start << 8;  // (node << 8) | depth
-        int8_t found = 0;
-        while (sp > 0) {
-            const uint64_t top = stk[--sp];
-            const uint64_t v = top >> 8;
-            const int depth = (int)(top & 0xFF);
-            if (!bit_get(g.valid, v)) continue;
-            uint64_t nb[4];
-            const int od = dev_outgoing(g, v, nb);
-            if (od == 0) continue;  // EdgeOutdegreeZero
-            if (depth >= limit) continue;
-            for (int j = 0; j < od; ++j) {
-                const uint64_t x = nb[j];
-                const bool nv = !gset_contains(vis, cv, x, gen);
-                const bool sr = (x == start && depth > 0);
-                if (nv || sr) {
-                    gset_insert(vis, cv, x, gen, vsize, over);
-                    if (sp >= cs) over = true;
-                    if (over) break;
-                    stk[sp++] = (x << 8) | (uint64_t)(depth + 1);
-                }
-            }
-            if (over) break;
-            if (v == start && depth > 1) { found = 1; break; }
-        }
-        res[i] = over ? -1 : found;
-    }
 }
 
 // (round 5) The same search with its visited set and stack in LDS (cf.dls_lds, default): a wave
@@ -1601,7 +1460,10 @@ struct PeelState {
     uint64_t slots = 0;
 };
 
-static void run_peel_rulers(mcaat_graph *g, const uint64_t *seed_bm, PeelState &ps) {
+// RecursiveReduction from every seed, as list ranking: work proportional to the graph, not to
+// the chains' length (counter-driven walks back from the seeds were the alternative: C3's
+// reduction walks chains of tens of thousands of edges from a few hundred seeds)
+static void run_peel(mcaat_graph *g, const uint64_t *seed_bm, PeelState &ps) {
     mcaat_ctx *ctx = g->ctx;
     hipStream_t st = ctx->stream;
     const uint64_t D = g->D;
@@ -1693,52 +1555,6 @@ static void run_peel_rulers(mcaat_graph *g, const uint64_t *seed_bm, PeelState &
     HIP_OK(hipStreamSynchronize(st));
 }
 
-// RecursiveReduction from every seed: counter-driven walks (work proportional to what is
-// removed) with a per-thread step budget; if chains are longer than that, the pending
-// frontier seeds the parallel ruler/list-ranking peel, whose fixpoint from this state is
-// the same (every pending node is valid, has no valid successor and must be removed).
-static void run_peel(mcaat_graph *g, const uint64_t *seed_bm, PeelState &ps) {
-    mcaat_ctx *ctx = g->ctx;
-    // C3: the reduction walks chains of tens of thousands of edges back from a few hundred
-    // seeds (budget 512: 164 walks still pending; 32768: 12, at 0.5 s), so by default the
-    // list-ranking peel runs alone from the seeds (the same fixpoint); cf.walk_budget > 0 runs
-    // counter-driven walks with that step budget first
-    const int64_t walk_budget = knob(ctx, "cf.walk_budget", 0);
-    if (walk_budget <= 0) {
-        run_peel_rulers(g, seed_bm, ps);
-        return;
-    }
-    const uint32_t kBudget = (uint32_t)std::min<int64_t>(walk_budget, 0xFFFFFFFFLL);
-    hipStream_t st = ctx->stream;
-    const uint64_t D = g->D, nw = g->n_words();
-    if (!D) return;
-    GraphView v = g->view();
-    DevBuf<unsigned long long> cur(2);
-    DevBuf<uint32_t> rem(D);
-    DevBuf<uint64_t> fa(D), fb(D), pend(D);
-    HIP_OK(hipMemsetAsync(cur.p, 0, 16, st));
-    launch_at(st, dim3(grid_for(nw * 64, kBlock)), dim3(kBlock), k_kahn_init, v, seed_bm, rem.p, fa.p, cur.p);
-    uint64_t n = read_counter(ctx, cur.p);
-    while (n) {
-        if (verbose()) fprintf(stderr, "[mcaat] peel: kahn frontier %llu\n", (unsigned long long)n);
-        HIP_OK(hipMemsetAsync(cur.p, 0, 8, st));
-        launch_at(st, dim3(grid_for(n, 64)), dim3(64), k_kahn_walk, v, rem.p, fa.p, n, fb.p, cur.p, kBudget, pend.p,
-                  cur.p + 1);
-        n = read_counter(ctx, cur.p);
-        std::swap(fa, fb);
-    }
-    const uint64_t np = read_counter(ctx, cur.p + 1);
-    if (verbose()) fprintf(stderr, "[mcaat] peel: pending after kahn walks %llu\n", (unsigned long long)np);
-    if (np) {
-        DevBuf<uint64_t> bm(nw);
-        HIP_OK(hipMemsetAsync(bm.p, 0, bm.bytes(), st));
-        launch_at(st, dim3(grid_for(np, kBlock)), dim3(kBlock), k_ids_to_bits, pend.p, np, bm.p);
-        PeelState own;  // no first pass done, one slot per edge
-        run_peel_rulers(g, bm.p, own);
-    }
-    HIP_OK(hipStreamSynchronize(st));
-}
-
 // ---------------------------- DLS driver -------------------------------------
 static std::vector<uint64_t> run_dls(mcaat_graph *g, const std::vector<uint64_t> &cand, int limit) {
     mcaat_ctx *ctx = g->ctx;
@@ -1827,15 +1643,11 @@ static std::vector<uint64_t> run_dls_dev(mcaat_graph *g, const uint64_t *dcand, 
     hipStream_t st = ctx->stream;
     std::vector<uint64_t> pass;
     if (!n) return pass;
-    // (round 4) cf.dls_persist=1: per-lane scratch, candidates strided over the lanes; 0 (default):
-    // one scratch slot per candidate in batches
-    // measured: C3 2.6 ms either way, C5 49.0 ms against 42.4 for the batches (a persistent
-    // wave runs its lanes' candidate sequences to the longest sum, and finished waves leave their
-    // CU idle): off by default
-    const bool persist = knob(ctx, "cf.dls_persist", 0) != 0;
-    // scratch budget of one launch (knob cf.dls_budget, GB)
+    // one scratch slot per candidate, in batches within the scratch budget of one launch (knob
+    // cf.dls_budget, GB). Per-lane scratch with the candidates strided over persistent lanes
+    // lost at C5, 49.0 ms against 42.4: finished waves leave their CU idle
     const uint64_t budget = (uint64_t)std::max<int64_t>(1, knob(ctx, "cf.dls_budget", 8)) << 30;
-    const bool many = !persist && n * 8ULL * (1024 + 2048) > budget;
+    const bool many = n * 8ULL * (1024 + 2048) > budget;
     uint32_t cs = (uint32_t)std::max<int64_t>(1, knob(ctx, "cf.dls_stack", many ? 128 : 1024));
     uint32_t cv = (uint32_t)next_pow2((uint64_t)std::max<int64_t>(2, knob(ctx, "cf.dls_visited", many ? 256 : 2048)));
     const int lanes = (int)std::max<int64_t>(1, std::min<int64_t>(64, knob(ctx, "cf.dls_lanes", 16)));
@@ -1854,7 +1666,7 @@ static std::vector<uint64_t> run_dls_dev(mcaat_graph *g, const uint64_t *dcand, 
     bool first = true;
     // (round 5) first pass in LDS (cf.dls_lds, default 1, graphs below 2^32 - 1 edges); what
     // overflows its tables continues below with global scratch at 8x the first caps
-    if (!persist && knob(ctx, "cf.dls_lds", 1) != 0 && g->D < 0xFFFFFFFFull && limit < 255) {
+    if (knob(ctx, "cf.dls_lds", 1) != 0 && g->D < 0xFFFFFFFFull && limit < 255) {
         DevBuf<int8_t> r(n);
         // cf.dls_lds_cap (tests): fewer visited / stack entries, so searches overflow to the re-run
         const uint32_t lc = (uint32_t)std::max<int64_t>(1, knob(ctx, "cf.dls_lds_cap", kLdsVis));
@@ -1874,24 +1686,12 @@ static std::vector<uint64_t> run_dls_dev(mcaat_graph *g, const uint64_t *dcand, 
             src = ids.p;
         }
         DevBuf<int8_t> r(nt);
-        if (persist) {
-            // scratch per lane: as many lanes as the GPU holds at once (or fewer candidates),
-            // within the same 8-GB scratch budget
-            const uint64_t nl = std::max<uint64_t>(
-                1, std::min<uint64_t>({nt, (uint64_t)ctx->n_cu * 32 * (uint64_t)lanes, batch_cap}));
-            DevBuf<uint64_t> dstk(nl * cs), dvis(nl * cv);
-            HIP_OK(hipMemsetAsync(dvis.p, 0, dvis.bytes(), st));
-            launch_at(st, dim3(grid_for(nl, (unsigned)lanes)), dim3(64), k_dls_lanes, g->view(), src, nt, limit, dstk.p, cs,
-                      dvis.p, cv, r.p, lanes, nl);
-            HIP_OK(hipStreamSynchronize(st));  // the scratch is freed on scope exit
-        } else {
-            for (uint64_t b0 = 0; b0 < nt; b0 += batch_cap) {
-                const uint64_t m = std::min<uint64_t>(batch_cap, nt - b0);
-                DevBuf<uint64_t> dstk(m * cs), dvis(m * cv);
-                launch_at(st, dim3(grid_for(m, (unsigned)lanes)), dim3(64), k_dls, g->view(), src + b0, m, limit, dstk.p, cs,
-                          dvis.p, cv, r.p + b0, lanes);
-                HIP_OK(hipStreamSynchronize(st));  // the batch's scratch is freed on scope exit
-            }
+        for (uint64_t b0 = 0; b0 < nt; b0 += batch_cap) {
+            const uint64_t m = std::min<uint64_t>(batch_cap, nt - b0);
+            DevBuf<uint64_t> dstk(m * cs), dvis(m * cv);
+            launch_at(st, dim3(grid_for(m, (unsigned)lanes)), dim3(64), k_dls, g->view(), src + b0, m, limit, dstk.p, cs,
+                      dvis.p, cv, r.p + b0, lanes);
+            HIP_OK(hipStreamSynchronize(st));  // the batch's scratch is freed on scope exit
         }
         nt = take_results(r, nt);
         if (nt) {
@@ -1951,6 +1751,39 @@ struct FcRunner {
         std::vector<uint16_t> lens;
     };
 
+    // One round's state, in the order its stages fill it (the stage that writes each member is
+    // named; everything is released when the round ends, the device buffers in reverse order)
+    struct Round {
+        uint64_t W = 0;   // the window: the first W pending starts
+        uint64_t Wl = 0;  // this rank's share of them (slots)
+        uint64_t pa = 0;  // bytes of scratch per search (the scratch's stride)
+        // search
+        DevBuf<uint64_t> dst;     // this rank's starts
+        DevBuf<uint8_t> scratch;  // its searches' scratch, slot i at i * pa (commit_round reads the lock tables)
+        DevBuf<FcStatus> dstat;
+        RankOut mine;  // statuses (search); nodes (several ranks) and cycle lengths (gather)
+        // gather: one GPU keeps the finished searches' nodes on the device, in slot order, with
+        // the start that owns each node, for commit_round and fetch_committed
+        DevBuf<uint64_t> dn_keep;
+        DevBuf<uint32_t> dj_keep;
+        // exchange: every rank's outputs (one GPU: ro[0] = &mine)
+        std::vector<RankOut> others;
+        std::vector<const RankOut *> ro;
+        // index_outputs: the window seen by start index j
+        std::vector<const FcStatus *> hs;  // status of start j
+        uint64_t first_bad = 0;            // the first start whose scratch overflowed (W: none)
+        std::vector<const uint64_t *> jn;  // nodes of start j on the host (null: none; one GPU: set by
+                                           // fetch_committed for the committed starts)
+        std::vector<const uint16_t *> jc;  // its cycle lengths
+        std::vector<uint64_t> joff;        // one GPU: start j's nodes at joff[j] of dn_keep
+        std::vector<uint32_t> selj;        // the starts before first_bad that found cycles
+        uint64_t n_nodes = 0;              //   and the nodes of their cycles
+        // commit_round
+        std::vector<uint8_t> skip;  // skip[j], j below the commit point: start j yields no entry
+        // fetch_committed
+        std::vector<uint64_t> hres;  // one GPU: the committed results' nodes (jn points into it)
+    };
+
     // Commit of one round on the device, in the reference's threads=1 order:
     //  (1) start j is skipped when it was visited before the round or when the cycles of an
     //      earlier committed start pass through it (k_fc_pairs finds the pairs; resolved in
@@ -1961,15 +1794,13 @@ struct FcRunner {
     //      table holds every node whose visited bit it read — contains a node first visited by
     //      an earlier start of the round (k_fc_conf, on the rank that ran j);
     //  the prefix before the first conflict or overflow commits (k_fc_mark sets its visited
-    //  bits) and the rest re-runs. Returns the commit point f; skip[j] for j < f.
-    uint64_t commit_round(const std::vector<uint64_t> &pending, uint64_t W, uint64_t first_bad,
-                          const std::vector<uint32_t> &selj, const std::vector<const uint64_t *> &jn,
-                          const std::vector<const FcStatus *> &hs, uint64_t n_nodes, const uint8_t *scratch,
-                          uint64_t pa, std::vector<uint8_t> &skip, const uint64_t *dev_nodes,
-                          const uint32_t *dev_owner) {
+    //  bits) and the rest re-runs. Returns the commit point f; r.skip[j] for j < f.
+    uint64_t commit_round(const std::vector<uint64_t> &pending, Round &r) {
         hipStream_t st = g->ctx->stream;
-        skip.assign(W, 0);
-        const uint32_t nb = (uint32_t)first_bad;
+        const uint64_t n_nodes = r.n_nodes;
+        std::vector<uint8_t> &skip = r.skip;
+        skip.assign(r.W, 0);
+        const uint32_t nb = (uint32_t)r.first_bad;
         if (nb == 0) return 0;
         const uint32_t scap = (uint32_t)next_pow2(2ULL * nb + 16);
         const uint32_t hcap = (uint32_t)next_pow2(2ULL * n_nodes + 16);
@@ -1983,15 +1814,15 @@ struct FcRunner {
         HIP_OK(hipMemsetAsync(dnp.p, 0, 8, st));
         // node lists of the starts with cycles, in start order, and each node's start (one GPU:
         // already on the device from the gather; several: assembled from every rank's outputs)
-        const uint64_t *dn = dev_nodes;
-        const uint32_t *dj = dev_owner;
+        const uint64_t *dn = r.dn_keep.p;
+        const uint32_t *dj = r.dj_keep.p;
         if (n_nodes && (!dn || !dj)) {
             std::vector<uint64_t> hn(n_nodes);
             std::vector<uint32_t> hj(n_nodes);
             uint64_t a = 0;
-            for (uint32_t j : selj) {
-                const uint64_t nn = hs[j]->nnodes;
-                std::copy(jn[j], jn[j] + nn, hn.begin() + a);
+            for (uint32_t j : r.selj) {
+                const uint64_t nn = r.hs[j]->nnodes;
+                std::copy(r.jn[j], r.jn[j] + nn, hn.begin() + a);
                 std::fill(hj.begin() + a, hj.begin() + a + nn, j);
                 a += nn;
             }
@@ -2003,14 +1834,11 @@ struct FcRunner {
             dj = djb.p;
             HIP_OK(hipStreamSynchronize(st));  // hn/hj go out of scope
         }
-        hipLaunchKernelGGL(k_fc_starts, dim3(grid_for(nb, kBlock)), dim3(kBlock), 0, st, dstarts.p, nb, skeys.p,
-                           svals.p, scap, dvis.p, prev.p);
-        LAUNCH_OK();
-        if (n_nodes) {
-            hipLaunchKernelGGL(k_fc_pairs, dim3(grid_for(n_nodes, kBlock)), dim3(kBlock), 0, st, dn, dj, n_nodes,
-                               skeys.p, svals.p, scap, dpairs.p, dnp.p);
-            LAUNCH_OK();
-        }
+        launch_at(st, dim3(grid_for(nb, kBlock)), dim3(kBlock), k_fc_starts, dstarts.p, nb, skeys.p, svals.p, scap, dvis.p,
+                  prev.p);
+        if (n_nodes)
+            launch_at(st, dim3(grid_for(n_nodes, kBlock)), dim3(kBlock), k_fc_pairs, dn, dj, n_nodes, skeys.p, svals.p, scap,
+                      dpairs.p, dnp.p);
         std::vector<uint8_t> pv(nb);
         unsigned long long np = 0;
         HIP_OK(hipMemcpyAsync(pv.data(), prev.p, nb, hipMemcpyDeviceToHost, st));
@@ -2025,15 +1853,13 @@ struct FcRunner {
         if (np) {
             DevBuf<uint64_t> k1(np), k2(np);
             DevBuf<unsigned long long> nu(1);
-            hipLaunchKernelGGL(k_fc_pair_keys, dim3(grid_for(np, kBlock)), dim3(kBlock), 0, st, (const uint64_t *)dpairs.p,
-                               (uint64_t)np, pb, k1.p);
-            LAUNCH_OK();
-            size_t t1 = 0, t2 = 0;
-            HIP_OK(hipcub::DeviceRadixSort::SortKeys(nullptr, t1, k1.p, k2.p, (int)np, 0, 2 * pb, st));
-            HIP_OK(hipcub::DeviceSelect::Unique(nullptr, t2, k2.p, k1.p, nu.p, (int)np, st));
-            DevBuf<uint8_t> tmp(std::max<size_t>({t1, t2, 1}));
-            HIP_OK(hipcub::DeviceRadixSort::SortKeys(tmp.p, t1, k1.p, k2.p, (int)np, 0, 2 * pb, st));
-            HIP_OK(hipcub::DeviceSelect::Unique(tmp.p, t2, k2.p, k1.p, nu.p, (int)np, st));
+            launch_at(st, dim3(grid_for(np, kBlock)), dim3(kBlock), k_fc_pair_keys, dpairs.p, np, pb, k1.p);
+            with_cub_temp([&](void *t, size_t &tmp) {
+                return hipcub::DeviceRadixSort::SortKeys(t, tmp, k1.p, k2.p, (int)np, 0, 2 * pb, st);
+            });
+            with_cub_temp([&](void *t, size_t &tmp) {
+                return hipcub::DeviceSelect::Unique(t, tmp, k2.p, k1.p, nu.p, (int)np, st);
+            });
             unsigned long long nuq = 0;
             d2h(g->ctx, &nuq, nu.p, 8);
             pairs.resize(nuq);
@@ -2054,14 +1880,12 @@ struct FcRunner {
         HIP_OK(hipMemcpyAsync(act.p, active.data(), nb, hipMemcpyHostToDevice, st));
         HIP_OK(hipMemsetAsync(hkeys.p, 0xFF, hkeys.bytes(), st));
         HIP_OK(hipMemsetAsync(hvals.p, 0xFF, hvals.bytes(), st));
-        if (n_nodes) {
-            hipLaunchKernelGGL(k_fc_first, dim3(grid_for(n_nodes, kBlock)), dim3(kBlock), 0, st, dn, dj, n_nodes,
-                               act.p, dvis.p, hkeys.p, hvals.p, hcap);
-            LAUNCH_OK();
-        }
+        if (n_nodes)
+            launch_at(st, dim3(grid_for(n_nodes, kBlock)), dim3(kBlock), k_fc_first, dn, dj, n_nodes, act.p, dvis.p, hkeys.p,
+                      hvals.p, hcap);
         verbose_mark(g->ctx, "fc.commit_first");
         // (3) conflicts: only starts that commit after some other start can conflict
-        uint64_t f = first_bad;
+        uint64_t f = r.first_bad;
         std::vector<uint32_t> jm, js;
         bool seen_commit = false;
         for (uint32_t j = 0; j < nb; ++j) {
@@ -2072,16 +1896,15 @@ struct FcRunner {
             }
             seen_commit = true;
         }
-        uint64_t my_first = W;
+        uint64_t my_first = r.W;
         if (n_nodes && !jm.empty()) {
             DevBuf<uint32_t> djm(jm.size()), djs(js.size());
             const unsigned int none = 0xFFFFFFFFu;
             HIP_OK(hipMemcpyAsync(dfirst.p, &none, 4, hipMemcpyHostToDevice, st));
             HIP_OK(hipMemcpyAsync(djm.p, jm.data(), 4 * jm.size(), hipMemcpyHostToDevice, st));
             HIP_OK(hipMemcpyAsync(djs.p, js.data(), 4 * js.size(), hipMemcpyHostToDevice, st));
-            hipLaunchKernelGGL(k_fc_conf, dim3((unsigned)jm.size()), dim3(64), 0, st, scratch, pa, caps.CL, djm.p,
-                               djs.p, (uint32_t)jm.size(), hkeys.p, hvals.p, hcap, dfirst.p);
-            LAUNCH_OK();
+            launch_at(st, dim3((unsigned)jm.size()), dim3(64), k_fc_conf, r.scratch.p, r.pa, caps.CL, djm.p, djs.p, jm.size(),
+                      hkeys.p, hvals.p, hcap, dfirst.p);
             unsigned int h = none;
             HIP_OK(hipMemcpyAsync(&h, dfirst.p, 4, hipMemcpyDeviceToHost, st));
             HIP_OK(hipStreamSynchronize(st));
@@ -2092,231 +1915,255 @@ struct FcRunner {
             for (uint64_t x : comm->allgather_one(my_first)) my_first = std::min(my_first, x);
         f = std::min(f, my_first);
         // commit [0, f): visited bits of the nodes its starts visit first
-        if (n_nodes && f > 0) {
-            hipLaunchKernelGGL(k_fc_mark, dim3(grid_for(hcap, kBlock)), dim3(kBlock), 0, st, hkeys.p, hvals.p, hcap,
-                               (uint32_t)f, dvis.p);
-            LAUNCH_OK();
-        }
+        if (n_nodes && f > 0)
+            launch_at(st, dim3(grid_for(hcap, kBlock)), dim3(kBlock), k_fc_mark, hkeys.p, hvals.p, hcap, f, dvis.p);
         HIP_OK(hipStreamSynchronize(st));
         return f;
     }
 
-    void run_bucket(const std::vector<uint64_t> &bucket) {
+    // ---- the stages of a round, in the order run_bucket calls them ----
+
+    // starts already visited are skipped by the reference (:476) -> no entry
+    void drop_visited(std::vector<uint64_t> &pending) {
         hipStream_t st = g->ctx->stream;
+        DevBuf<uint64_t> ids(pending.size());
+        DevBuf<uint8_t> bits(pending.size());
+        std::vector<uint8_t> hb(pending.size());
+        HIP_OK(hipMemcpyAsync(ids.p, pending.data(), 8 * pending.size(), hipMemcpyHostToDevice, st));
+        launch_at(st, dim3(grid_for(pending.size(), kBlock)), dim3(kBlock), k_get_bits, dvis.p, ids.p, pending.size(), bits.p);
+        HIP_OK(hipMemcpyAsync(hb.data(), bits.p, pending.size(), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        std::vector<uint64_t> keep;
+        keep.reserve(pending.size());
+        for (size_t i = 0; i < pending.size(); ++i)
+            if (!hb[i]) keep.push_back(pending[i]);
+        pending.swap(keep);
+    }
+
+    // this rank's searches of the window (start R + N * i in slot i) against the visited snapshot
+    void search(const std::vector<uint64_t> &pending, Round &r) {
+        hipStream_t st = g->ctx->stream;
+        const uint64_t Wl = r.Wl;
+        r.dst.alloc(Wl);
+        r.scratch.alloc(Wl * r.pa);
+        r.dstat.alloc(Wl);
+        r.mine.st.resize(Wl);
+        if (!Wl) return;
+        std::vector<uint64_t> ls(Wl);
+        for (uint64_t i = 0; i < Wl; ++i) ls[i] = pending[R + N * i];
+        HIP_OK(hipMemcpyAsync(r.dst.p, ls.data(), 8 * Wl, hipMemcpyHostToDevice, st));
+        // one search per one-wave workgroup (more searches per wave serialise each
+        // other's divergent branches: measured 64 per wave 93 ms, 16: 44, 4: 30, 1: 23 at C3)
+        hipLaunchKernelGGL(k_findcycle, dim3((unsigned)Wl), dim3(64), fc_lds_bytes(caps), st, g->view(), dvis.p, r.dst.p, Wl,
+                           caps, prm, (uint64_t *)r.scratch.p, r.dstat.p);
+        LAUNCH_OK();
+        d2h(g->ctx, r.mine.st.data(), r.dstat.p, Wl * sizeof(FcStatus));
+    }
+
+    // MCAAT_VERBOSE: the round's totals and its five longest searches
+    void report(const Round &r) const {
+        const std::vector<FcStatus> &s = r.mine.st;
+        if (!verbose() || s.empty()) return;
+        std::vector<uint64_t> ord(s.size());
+        for (uint64_t i = 0; i < ord.size(); ++i) ord[i] = i;
+        const size_t top = std::min<size_t>(5, ord.size());
+        std::partial_sort(ord.begin(), ord.begin() + top, ord.end(),
+                          [&](uint64_t a, uint64_t b) { return s[a].steps > s[b].steps; });
+        uint64_t tot = 0, trl = 0, mlk = 0;
+        for (const auto &x : s) {
+            tot += x.steps;
+            trl += x.relax;
+            mlk = std::max<uint64_t>(mlk, x.locks);
+        }
+        fprintf(stderr, "[mcaat] fc: %llu searches, %llu steps, %llu relaxations, max locks %llu; longest:",
+                (unsigned long long)s.size(), (unsigned long long)tot, (unsigned long long)trl, (unsigned long long)mlk);
+        for (size_t q = 0; q < top; ++q)
+            fprintf(stderr, " %u (relax %u, locks %u, ncyc %d, nodes %u)", s[ord[q]].steps, s[ord[q]].relax, s[ord[q]].locks,
+                    s[ord[q]].ncyc, s[ord[q]].nnodes);
+        fprintf(stderr, "\n");
+    }
+
+    // the nodes and cycle lengths of this rank's finished searches (status 0) with cycles, in
+    // slot order, out of the scratch
+    void gather(Round &r) {
+        hipStream_t st = g->ctx->stream;
+        RankOut &mine = r.mine;
+        std::vector<uint64_t> sel, noff{0}, coff{0};
+        for (uint64_t i = 0; i < r.Wl; ++i) {
+            if (mine.st[i].status != 0 && N == 1) break;  // one GPU: nothing past the first overflow is used
+            if (mine.st[i].status == 0 && mine.st[i].ncyc > 0) {
+                sel.push_back(i);
+                noff.push_back(noff.back() + mine.st[i].nnodes);
+                coff.push_back(coff.back() + mine.st[i].ncyc);
+            }
+        }
+        // (round 6) one GPU: the nodes stay on the device until the commit says which
+        // starts' cycles are results (a window's skipped starts often hold most of them)
+        if (N > 1) mine.nodes.resize(noff.back());
+        mine.lens.resize(coff.back());
+        if (sel.empty()) return;
+        DevBuf<uint64_t> dsel(sel.size()), dno(noff.size()), dco(coff.size()), dn(noff.back());
+        DevBuf<uint16_t> dl(coff.back());
+        HIP_OK(hipMemcpyAsync(dsel.p, sel.data(), 8 * sel.size(), hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(dno.p, noff.data(), 8 * noff.size(), hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(dco.p, coff.data(), 8 * coff.size(), hipMemcpyHostToDevice, st));
+        launch_at(st, dim3((unsigned)sel.size()), dim3(256), k_fc_gather, (const uint64_t *)r.scratch.p, r.pa, caps, dsel.p,
+                  dno.p, dco.p, dn.p, dl.p, sel.size());
+        if (N > 1) d2h(g->ctx, mine.nodes.data(), dn.p, 8 * mine.nodes.size());
+        d2h(g->ctx, mine.lens.data(), dl.p, 2 * mine.lens.size());
+        if (N == 1) {  // one GPU: slot i is start i
+            r.dj_keep.alloc(noff.back());
+            launch_at(st, dim3((unsigned)sel.size()), dim3(256), k_fc_owner, dsel.p, dno.p, r.dj_keep.p, sel.size());
+            r.dn_keep = std::move(dn);
+        }
+        HIP_OK(hipStreamSynchronize(st));
+    }
+
+    // every rank's outputs (one GPU: its own)
+    void exchange(Round &r) {
+        r.ro.resize(N);
+        if (N == 1) {
+            r.ro[0] = &r.mine;
+            return;
+        }
+        r.others.resize(N);
+        std::vector<uint64_t> cs, cn, cl;
+        auto st_all = comm->allgather_vec(r.mine.st, &cs);
+        auto nd_all = comm->allgather_vec(r.mine.nodes, &cn);
+        auto ln_all = comm->allgather_vec(r.mine.lens, &cl);
+        uint64_t a = 0, b = 0, c = 0;
+        for (int q = 0; q < N; ++q) {
+            r.others[q].st.assign(st_all.begin() + a, st_all.begin() + a + cs[q]);
+            r.others[q].nodes.assign(nd_all.begin() + b, nd_all.begin() + b + cn[q]);
+            r.others[q].lens.assign(ln_all.begin() + c, ln_all.begin() + c + cl[q]);
+            a += cs[q];
+            b += cn[q];
+            c += cl[q];
+            r.ro[q] = &r.others[q];
+        }
+    }
+
+    // the window by start index: the status of start j and, for the starts before the first
+    // overflow that found cycles, where their nodes and lengths are. Each rank's outputs are in
+    // slot order, and only those starts are used (one GPU gathers nothing past the overflow)
+    void index_outputs(Round &r) {
+        const uint64_t W = r.W;
+        r.hs.resize(W);
+        r.first_bad = W;
+        for (uint64_t j = 0; j < W; ++j) {
+            r.hs[j] = &r.ro[j % N]->st[j / N];
+            if (r.hs[j]->status != 0 && r.first_bad == W) r.first_bad = j;
+        }
+        r.jn.assign(W, nullptr);
+        r.jc.assign(W, nullptr);
+        r.joff.assign(N == 1 ? W : 0, 0);
+        std::vector<uint64_t> nptr(N, 0), cptr(N, 0);
+        for (uint64_t j = 0; j < r.first_bad; ++j) {
+            const int o = (int)(j % N);
+            const FcStatus &s = *r.hs[j];
+            if (s.ncyc <= 0) continue;
+            if (N == 1) r.joff[j] = nptr[o];
+            else r.jn[j] = r.ro[o]->nodes.data() + nptr[o];
+            r.jc[j] = r.ro[o]->lens.data() + cptr[o];
+            nptr[o] += s.nnodes;
+            cptr[o] += s.ncyc;
+            r.selj.push_back((uint32_t)j);
+            r.n_nodes += s.nnodes;
+        }
+    }
+
+    // whether start j (below the commit point) yields nodes to fetch from the device
+    static bool has_nodes(const Round &r, uint64_t j) { return !r.skip[j] && r.hs[j]->ncyc > 0 && r.hs[j]->nnodes; }
+
+    // one GPU: the committed results' nodes, gathered from the device in one copy
+    void fetch_committed(Round &r, uint64_t f) {
+        if (N != 1 || !r.dn_keep.p) return;
+        std::vector<uint64_t> seg;
+        uint64_t tot = 0;
+        for (uint64_t j = 0; j < f; ++j)
+            if (has_nodes(r, j)) {
+                seg.insert(seg.end(), {r.joff[j], (uint64_t)r.hs[j]->nnodes, tot});
+                tot += r.hs[j]->nnodes;
+            }
+        if (!tot) return;
+        DevBuf<uint64_t> dseg(seg.size()), dres(tot);
+        h2d(g->ctx, dseg.p, seg.data(), 8 * seg.size());
+        launch_at(g->ctx->stream, dim3((unsigned)(seg.size() / 3)), dim3(256), k_fc_segs, r.dn_keep.p, dseg.p, dres.p);
+        r.hres.resize(tot);
+        d2h(g->ctx, r.hres.data(), dres.p, 8 * tot);
+        uint64_t at = 0;
+        for (uint64_t j = 0; j < f; ++j)
+            if (has_nodes(r, j)) {
+                r.jn[j] = r.hres.data() + at;
+                at += r.hs[j]->nnodes;
+            }
+    }
+
+    // results of the committed prefix [0, f)
+    void append_results(const std::vector<uint64_t> &pending, const Round &r, uint64_t f) {
+        for (uint64_t j = 0; j < f; ++j) {
+            if (r.skip[j]) continue;
+            out->starts.push_back(pending[j]);
+            std::vector<uint64_t> fl, of{0};
+            if (r.jn[j]) {
+                fl.assign(r.jn[j], r.jn[j] + r.hs[j]->nnodes);
+                for (int32_t c = 0; c < r.hs[j]->ncyc; ++c) of.push_back(of.back() + r.jc[j][c]);
+            }
+            out->stats[5] += of.size() - 1;
+            out->flat.push_back(std::move(fl));
+            out->offsets.push_back(std::move(of));
+        }
+    }
+
+    // the commit stopped at a scratch overflow: grow the exhausted structure for the re-run
+    void grow_caps(const Round &r, uint64_t f) {
+        if (f != r.first_bad || r.first_bad >= r.W) return;
+        const int code = r.hs[f]->status;
+        if (code == 1) caps.CL *= 4;
+        else if (code == 2) caps.CR *= 4;
+        else caps.CO *= 2;
+        if (caps.CL > (1u << 26) || caps.CR > (1u << 26) || caps.CO > (1u << 28))
+            throw Error(MCAAT_E_CAPACITY, "FindCycle scratch exceeded its growth limit");
+    }
+
+    // the speculation window adapted to the observed conflict rate
+    uint64_t next_window(uint64_t window, uint64_t W, uint64_t f) const {
+        const uint64_t wmax = 8192ULL * N;
+        if (f < W / 4) return std::max<uint64_t>(16, window / 2);
+        if (f == W) return std::min<uint64_t>(wmax, window * 2);
+        return window;
+    }
+
+    void run_bucket(const std::vector<uint64_t> &bucket) {
+        mcaat_ctx *ctx = g->ctx;
         std::vector<uint64_t> pending(bucket);
-        uint64_t window = (uint64_t)std::max<int64_t>(1, knob(g->ctx, "cf.fc_window", 8192));
+        uint64_t window = (uint64_t)std::max<int64_t>(1, knob(ctx, "cf.fc_window", 8192));
         if (N > 1) window *= (uint64_t)N;  // each rank keeps the single-GPU window of searches
         while (!pending.empty()) {
-            // starts already visited are skipped by the reference (:476) -> no entry
-            {
-                DevBuf<uint64_t> ids(pending.size());
-                DevBuf<uint8_t> bits(pending.size());
-                std::vector<uint8_t> hb(pending.size());
-                HIP_OK(hipMemcpyAsync(ids.p, pending.data(), 8 * pending.size(), hipMemcpyHostToDevice, st));
-                hipLaunchKernelGGL(k_get_bits, dim3(grid_for(pending.size(), kBlock)), dim3(kBlock), 0, st, dvis.p, ids.p,
-                                   (uint64_t)pending.size(), bits.p);
-                LAUNCH_OK();
-                HIP_OK(hipMemcpyAsync(hb.data(), bits.p, pending.size(), hipMemcpyDeviceToHost, st));
-                HIP_OK(hipStreamSynchronize(st));
-                std::vector<uint64_t> keep;
-                keep.reserve(pending.size());
-                for (size_t i = 0; i < pending.size(); ++i)
-                    if (!hb[i]) keep.push_back(pending[i]);
-                pending.swap(keep);
-            }
+            drop_visited(pending);
             if (pending.empty()) break;
             ++rounds;
-            const uint64_t W = std::min<uint64_t>(window, pending.size());
-            const uint64_t Wl = W > (uint64_t)R ? (W - R + N - 1) / N : 0;  // this rank's starts
-            const uint64_t pa = per_al();
-            DevBuf<uint64_t> dst(Wl);
-            DevBuf<uint8_t> scratch(Wl * pa);
-            DevBuf<FcStatus> dstat(Wl);
-            RankOut mine;
-            mine.st.resize(Wl);
-            if (Wl) {
-                std::vector<uint64_t> ls(Wl);
-                for (uint64_t i = 0; i < Wl; ++i) ls[i] = pending[R + N * i];
-                HIP_OK(hipMemcpyAsync(dst.p, ls.data(), 8 * Wl, hipMemcpyHostToDevice, st));
-                // one search per one-wave workgroup (more searches per wave serialise each
-                // other's divergent branches: measured 64 per wave 93 ms, 16: 44, 4: 30, 1: 23 at C3)
-                hipLaunchKernelGGL(k_findcycle, dim3((unsigned)Wl), dim3(64), fc_lds_bytes(caps), st, g->view(), dvis.p,
-                                   dst.p, Wl, caps, prm, (uint64_t *)scratch.p, dstat.p);
-                LAUNCH_OK();
-                d2h(g->ctx, mine.st.data(), dstat.p, Wl * sizeof(FcStatus));
-            }
-            verbose_mark(g->ctx, "fc.round_kernel");
-            if (verbose() && Wl) {
-                std::vector<uint64_t> ord(Wl);
-                for (uint64_t i = 0; i < Wl; ++i) ord[i] = i;
-                const size_t top = std::min<size_t>(5, ord.size());
-                std::partial_sort(ord.begin(), ord.begin() + top, ord.end(),
-                                  [&](uint64_t a, uint64_t b) { return mine.st[a].steps > mine.st[b].steps; });
-                uint64_t tot = 0, trl = 0, mlk = 0;
-                for (const auto &x : mine.st) {
-                    tot += x.steps;
-                    trl += x.relax;
-                    mlk = std::max<uint64_t>(mlk, x.locks);
-                }
-                fprintf(stderr, "[mcaat] fc: %llu searches, %llu steps, %llu relaxations, max locks %llu; longest:",
-                        (unsigned long long)Wl, (unsigned long long)tot, (unsigned long long)trl,
-                        (unsigned long long)mlk);
-                for (size_t q = 0; q < top; ++q)
-                    fprintf(stderr, " %u (relax %u, locks %u, ncyc %d, nodes %u)", mine.st[ord[q]].steps,
-                            mine.st[ord[q]].relax, mine.st[ord[q]].locks, mine.st[ord[q]].ncyc, mine.st[ord[q]].nnodes);
-                fprintf(stderr, "\n");
-            }
-            // this rank's finished searches (status 0) with cycles, in slot order; on one GPU
-            // their nodes stay on the device for the commit (dn_keep, node -> start in dj_keep)
-            DevBuf<uint64_t> dn_keep;
-            DevBuf<uint32_t> dj_keep;
-            {
-                std::vector<uint64_t> sel, noff{0}, coff{0};
-                for (uint64_t i = 0; i < Wl; ++i) {
-                    if (mine.st[i].status != 0 && N == 1) break;  // one GPU: nothing past the first overflow is used
-                    if (mine.st[i].status == 0 && mine.st[i].ncyc > 0) {
-                        sel.push_back(i);
-                        noff.push_back(noff.back() + mine.st[i].nnodes);
-                        coff.push_back(coff.back() + mine.st[i].ncyc);
-                    }
-                }
-                // (round 6) one GPU: the nodes stay on the device until the commit says which
-                // starts' cycles are results (a window's skipped starts often hold most of them)
-                if (N > 1) mine.nodes.resize(noff.back());
-                mine.lens.resize(coff.back());
-                if (!sel.empty()) {
-                    DevBuf<uint64_t> dsel(sel.size()), dno(noff.size()), dco(coff.size()), dn(noff.back());
-                    DevBuf<uint16_t> dl(coff.back());
-                    HIP_OK(hipMemcpyAsync(dsel.p, sel.data(), 8 * sel.size(), hipMemcpyHostToDevice, st));
-                    HIP_OK(hipMemcpyAsync(dno.p, noff.data(), 8 * noff.size(), hipMemcpyHostToDevice, st));
-                    HIP_OK(hipMemcpyAsync(dco.p, coff.data(), 8 * coff.size(), hipMemcpyHostToDevice, st));
-                    hipLaunchKernelGGL(k_fc_gather, dim3((unsigned)sel.size()), dim3(256), 0, st, (uint64_t *)scratch.p,
-                                       pa, caps, dsel.p, dno.p, dco.p, dn.p, dl.p, (uint64_t)sel.size());
-                    LAUNCH_OK();
-                    if (N > 1) d2h(g->ctx, mine.nodes.data(), dn.p, 8 * mine.nodes.size());
-                    d2h(g->ctx, mine.lens.data(), dl.p, 2 * mine.lens.size());
-                    if (N == 1) {  // one GPU: slot i is start i
-                        dj_keep.alloc(noff.back());
-                        hipLaunchKernelGGL(k_fc_owner, dim3((unsigned)sel.size()), dim3(256), 0, st, dsel.p, dno.p,
-                                           dj_keep.p, (uint64_t)sel.size());
-                        LAUNCH_OK();
-                        dn_keep = std::move(dn);
-                    }
-                    HIP_OK(hipStreamSynchronize(st));
-                }
-            }
-            verbose_mark(g->ctx, "fc.gather_nodes");
-            // every rank's outputs (one GPU: its own)
-            std::vector<RankOut> others;
-            std::vector<const RankOut *> ro(N);
-            if (N == 1) {
-                ro[0] = &mine;
-            } else {
-                others.resize(N);
-                std::vector<uint64_t> cs, cn, cl;
-                auto st_all = comm->allgather_vec(mine.st, &cs);
-                auto nd_all = comm->allgather_vec(mine.nodes, &cn);
-                auto ln_all = comm->allgather_vec(mine.lens, &cl);
-                uint64_t a = 0, b = 0, c = 0;
-                for (int r = 0; r < N; ++r) {
-                    others[r].st.assign(st_all.begin() + a, st_all.begin() + a + cs[r]);
-                    others[r].nodes.assign(nd_all.begin() + b, nd_all.begin() + b + cn[r]);
-                    others[r].lens.assign(ln_all.begin() + c, ln_all.begin() + c + cl[r]);
-                    a += cs[r];
-                    b += cn[r];
-                    c += cl[r];
-                    ro[r] = &others[r];
-                }
-            }
-            // global view: status of start j and, for starts with cycles, their nodes/lengths
-            std::vector<const FcStatus *> hs(W);
-            uint64_t first_bad = W;
-            for (uint64_t j = 0; j < W; ++j) {
-                hs[j] = &ro[j % N]->st[j / N];
-                if (hs[j]->status != 0 && first_bad == W) first_bad = j;
-            }
-            std::vector<const uint64_t *> jn(W, nullptr);
-            std::vector<const uint16_t *> jc(W, nullptr);
-            std::vector<uint64_t> joff(N == 1 ? W : 0);  // one GPU: start j's nodes at joff[j] on the device
-            std::vector<uint32_t> selj;  // starts before the first overflow that found cycles
-            uint64_t n_nodes = 0;
-            {
-                // each rank's outputs are in slot order; only starts before the first overflow
-                // are used (one GPU gathers nothing past it)
-                std::vector<uint64_t> nptr(N, 0), cptr(N, 0);
-                for (uint64_t j = 0; j < first_bad; ++j) {
-                    const int o = (int)(j % N);
-                    if (hs[j]->ncyc > 0) {
-                        if (N == 1) joff[j] = nptr[o];
-                        else jn[j] = ro[o]->nodes.data() + nptr[o];
-                        jc[j] = ro[o]->lens.data() + cptr[o];
-                        nptr[o] += hs[j]->nnodes;
-                        cptr[o] += hs[j]->ncyc;
-                        selj.push_back((uint32_t)j);
-                        n_nodes += hs[j]->nnodes;
-                    }
-                }
-            }
-            verbose_mark(g->ctx, "fc.round_gather");
-            std::vector<uint8_t> skip;
-            const uint64_t f = commit_round(pending, W, first_bad, selj, jn, hs, n_nodes, scratch.p, pa, skip,
-                                            dn_keep.p ? dn_keep.p : nullptr, dj_keep.p ? dj_keep.p : nullptr);
-            verbose_mark(g->ctx, "fc.commit_device");
-            // one GPU: the committed results' nodes, gathered from the device in one copy
-            std::vector<uint64_t> hres;
-            if (N == 1 && dn_keep.p) {
-                std::vector<uint64_t> seg;
-                uint64_t tot = 0;
-                for (uint64_t j = 0; j < f; ++j)
-                    if (!skip[j] && hs[j]->ncyc > 0 && hs[j]->nnodes) {
-                        seg.insert(seg.end(), {joff[j], (uint64_t)hs[j]->nnodes, tot});
-                        tot += hs[j]->nnodes;
-                    }
-                if (tot) {
-                    DevBuf<uint64_t> dseg(seg.size()), dres(tot);
-                    h2d(g->ctx, dseg.p, seg.data(), 8 * seg.size());
-                    hipLaunchKernelGGL(k_fc_segs, dim3((unsigned)(seg.size() / 3)), dim3(256), 0, st,
-                                       (const uint64_t *)dn_keep.p, (const uint64_t *)dseg.p, dres.p);
-                    LAUNCH_OK();
-                    hres.resize(tot);
-                    d2h(g->ctx, hres.data(), dres.p, 8 * tot);
-                    uint64_t at = 0;
-                    for (uint64_t j = 0; j < f; ++j)
-                        if (!skip[j] && hs[j]->ncyc > 0 && hs[j]->nnodes) {
-                            jn[j] = hres.data() + at;
-                            at += hs[j]->nnodes;
-                        }
-                }
-            }
-            // results of the committed prefix [0, f)
-            for (uint64_t j = 0; j < f; ++j) {
-                if (skip[j]) continue;
-                out->starts.push_back(pending[j]);
-                std::vector<uint64_t> fl, of{0};
-                if (jn[j]) {
-                    fl.assign(jn[j], jn[j] + hs[j]->nnodes);
-                    for (int32_t c = 0; c < hs[j]->ncyc; ++c) of.push_back(of.back() + jc[j][c]);
-                }
-                out->stats[5] += of.size() - 1;
-                out->flat.push_back(std::move(fl));
-                out->offsets.push_back(std::move(of));
-            }
-            verbose_mark(g->ctx, "fc.round_commit");
-            if (f < W) ++reruns;
-            if (f == first_bad && first_bad < W) {
-                // scratch overflow at position f: grow the exhausted structure and re-run
-                const int code = hs[f]->status;
-                if (code == 1) caps.CL *= 4;
-                else if (code == 2) caps.CR *= 4;
-                else caps.CO *= 2;
-                if (caps.CL > (1u << 26) || caps.CR > (1u << 26) || caps.CO > (1u << 28))
-                    throw Error(MCAAT_E_CAPACITY, "FindCycle scratch exceeded its growth limit");
-            }
+            Round r;
+            r.W = std::min<uint64_t>(window, pending.size());
+            r.Wl = r.W > (uint64_t)R ? (r.W - R + N - 1) / N : 0;
+            r.pa = per_al();
+            search(pending, r);
+            verbose_mark(ctx, "fc.round_kernel");
+            report(r);
+            gather(r);
+            verbose_mark(ctx, "fc.gather_nodes");
+            exchange(r);
+            index_outputs(r);
+            verbose_mark(ctx, "fc.round_gather");
+            const uint64_t f = commit_round(pending, r);
+            verbose_mark(ctx, "fc.commit_device");
+            fetch_committed(r, f);
+            append_results(pending, r, f);
+            verbose_mark(ctx, "fc.round_commit");
+            if (f < r.W) ++reruns;
+            grow_caps(r, f);
             pending.erase(pending.begin(), pending.begin() + f);
-            // adapt the speculation window to the observed conflict rate
-            const uint64_t wmax = 8192ULL * N;
-            if (f < W / 4) window = std::max<uint64_t>(16, window / 2);
-            else if (f == W) window = std::min<uint64_t>(wmax, window * 2);
+            window = next_window(window, r.W, f);
         }
     }
 };
@@ -2375,7 +2222,6 @@ struct CfRun {
     // DepthLevelSearch straight from the device list (one GPU; cf.dls_host=1: through the host)
     const bool dev_dls;
     const int64_t scan_u;  // cf.scan_u: words in flight per wave in the scans (1, 2, 4)
-    const bool walks;      // cf.walk_budget > 0: counter-driven walks ahead of the list-ranking peel
 
     // ---- what crosses a stage boundary: the stage that writes it -> the last one that reads it
     DevBuf<uint64_t> seeds;       // tips before the multiplicity filter (whole graph): tips_filter -> peel
@@ -2396,8 +2242,7 @@ struct CfRun {
         : g(gr), ctx(gr->ctx), st(gr->ctx->stream), comm(c), N(c ? c->world : 1), R(c ? c->rank : 0), D(gr->D),
           nw(gr->n_words()), w_lo(nw * (uint64_t)R / (uint64_t)N), w_hi(nw * (uint64_t)(R + 1) / (uint64_t)N),
           wgrid(grid_for(nw * 64, kBlock, (unsigned)gr->ctx->n_cu * 16)), p(pa), out(res),
-          dev_dls(!c && knob(gr->ctx, "cf.dls_host", 0) == 0), scan_u(knob(gr->ctx, "cf.scan_u", kScanUDefault)),
-          walks(knob(gr->ctx, "cf.walk_budget", 0) > 0) {}
+          dev_dls(!c && knob(gr->ctx, "cf.dls_host", 0) == 0), scan_u(knob(gr->ctx, "cf.scan_u", kScanUDefault)) {}
 
     // bytes of each rank's words of a bitmap (the all-gathers' sizes)
     std::vector<uint64_t> word_bytes() const {
@@ -2410,9 +2255,9 @@ struct CfRun {
     // InvalidateMultiplicityOneNodes (the filtered bits go to a second bitmap), with the peel's
     // first pass, the recount's tips and ChunkStartNodes' candidate filter
     void tips_filter() {
-        // the list-ranking peel gets its first pass from this one (cf.fused_init=0, several ranks
-        // or walks ahead of it: its own k_peel_init)
-        fuse = !comm && !walks && knob(ctx, "cf.fused_init", 1) != 0 && D;
+        // the peel gets its first pass from this one (cf.fused_init=0 or several ranks: its own
+        // k_peel_init)
+        fuse = !comm && knob(ctx, "cf.fused_init", 1) != 0 && D;
         // every edge valid (as built): the passes before the filter read no unfiltered bitmap
         const bool fresh = g->all_valid && knob(ctx, "cf.fresh", 1) != 0;
         g->all_valid = false;  // the filter and the peel clear bits from here on
@@ -2491,7 +2336,7 @@ struct CfRun {
     // (round 6) cf.compact unset: compact when the filter keeps under cf.compact_pct % (30) of a
     // fresh graph's edges. C5 keeps 18 %; C3 keeps 59 % and stays per id
     bool compact_slots(bool fresh, const unsigned long long *cnt) {
-        if (!D || D >= (1ULL << 32) || walks) return false;
+        if (!D || D >= (1ULL << 32)) return false;
         if (knob_set(ctx, "cf.compact")) return knob(ctx, "cf.compact", 0) != 0;
         if (!fresh || !fuse) return false;
         unsigned long long low = 0;  // every mult <= 1 edge: on a fresh graph, the edges the filter clears

@@ -88,11 +88,7 @@ KNOBS = {
     # scratch regrowth in DepthLevelSearch and FindCycle, one speculative start per round
     "cf_scratch": {"cf.dls_stack": 1, "cf.dls_visited": 2, "cf.fc_lock": 4, "cf.fc_relax": 1, "cf.fc_out": 1,
                    "cf.fc_window": 1},
-    # counter-driven peel walks first: one step before the list-ranking peel takes over, or
-    # (nearly) unbounded walks that finish every chain themselves
-    "peel_walk1": {"cf.walk_budget": 1},
-    "peel_kahn": {"cf.walk_budget": 1 << 30},
-    # list-ranking peel with every unary node a ruler (one-step walks, deep super-ruler chains)
+    # the peel with every unary node a ruler (one-step walks, deep super-ruler chains)
     # and with sparse rulers (long walks, few super rulers)
     "peel_dense_rulers": {"cf.ruler_mask": 0},
     "peel_sparse_rulers": {"cf.ruler_mask": 4095},
@@ -117,9 +113,6 @@ KNOBS = {
     "peel_compact_own_init": {"cf.compact": 1, "cf.fused_init": 0},
     "tips_not_fresh": {"cf.fresh": 0},
     "compact_lists_regrow": {"cf.compact": 1, "cf.peel_list_cap": 1, "cf.cand_cap": 1, "cf.fresh": 0},
-    # (round 4) DepthLevelSearch with per-lane scratch instead of per-candidate batches
-    "dls_persist": {"cf.dls_persist": 1},
-    "dls_persist_regrow": {"cf.dls_persist": 1, "cf.dls_stack": 1, "cf.dls_visited": 2},
     # passes B and C of successive groups in turn on one stream
     "nc_no_overlap": {"nc.overlap": 0, "nc.group_budget": 1 << 14},
     # adjacency: per-edge global directory searches; the owner-side runs (default) with every
@@ -200,7 +193,7 @@ def test_forced_branches_really_taken(gpu_ctx):
 def test_retired_knobs_are_unknown(gpu_ctx):
     """The CycleFinder knobs whose paths are gone answer MCAAT_E_INVALID (-1) like any unknown
     name; a surviving knob is still accepted."""
-    for name in ("cf.pull_flags", "cf.recount"):
+    for name in ("cf.pull_flags", "cf.recount", "cf.walk_budget", "cf.dls_persist"):
         with pytest.raises(M.McaatError) as err:
             gpu_ctx.set_knob(name, 1)
         assert err.value.code == -1, name

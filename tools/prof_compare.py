@@ -26,6 +26,7 @@ while True:
     except FileNotFoundError:
         break
     r += 1
+# (k_dls_lanes is gone from the library; the name stays for profiles recorded while it existed)
 ONE = {"adjacency": ["k_adjacency_own", "k_own_bounds", "k_dir"],
        "cf_dwide": ["k_post_filter", "k_tips_filter", "k_peel_prep", "k_peel_walk", "k_peel_super", "k_peel_jump",
                     "k_peel_final", "k_peel_branch", "k_peel_apply_list", "k_peel_apply_rulers", "k_popcount",
