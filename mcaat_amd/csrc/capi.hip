@@ -1094,7 +1094,7 @@ int mcaat_set_knob(mcaat_ctx *ctx, const char *name, int64_t value) {
         "sort.block_limit", "cf.dls_stack",      "cf.dls_visited", "cf.fc_lock", "cf.fc_relax",
         "cf.fc_out",       "cf.fc_window",       "sdbg.adj_lds",   "sdbg.adj_cap",       "cf.ruler_mask",
         "nc.overlap",      "sort.l3_counting",   "cf.peel_list_div", "cf.peel_list_cap", "cf.cand_cap",
-        "fq.hostpack",     "sort.mid_counting", "nc.big_table", "cf.fused_init", "sort.mid_occ", "cf.scan_u", "cf.prep_batch", "cf.dls_lanes", "dist.oriented",
+        "fq.hostpack",     "nc.big_table", "cf.fused_init", "sort.mid_occ", "cf.dls_lanes", "dist.oriented",
         "sort.small_mid", "sort.small_limit", "cf.dls_host",
         "dist.desc",      "cf.compact",         "cf.fresh",   "nc.split_first", "nc.split_max", "cf.dls_budget", "nc.grow_early",
         "nc.free_sync", "dist.shard_cf", "dist.ruler_mask", "dist.adj_chunk", "dist.dir_edges", "nc.ahead", "dist.adj_ranges", "dist.win_ranges", "cf.dls_lds", "cf.dls_lds_cap", "dist.segs_at_one", "nc.a_mini", "nc.a_adapt", "nc.a_stats", "dist.bfs_sync", "cf.compact_pct", "dist.bfs_block", "dist.bfs_frontier", "dist.res_fixed", "dist.res_batch", "dist.res_block_mb", "dist.walk_block", "dist.walk_batch", "dist.grid_blocks", "dist.preagg"};

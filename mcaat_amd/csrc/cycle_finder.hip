@@ -102,11 +102,12 @@ struct PeelArrays {
 // is a popcount of at most two bitmap words (no per-successor loads); the in-edges of e are the
 // positions of a 16-bit mask inside the group starting at in_lo, so the valid in-degree and the
 // self-loop test of the candidate filter are two bitmap words as well
-// (knob cf.scan_u). More words per wave means fewer waves: C3 recount with 1 / 2 / 4 / 8 words
-// 5.5 / 5.7 / 8.3 / 18.0 ms (79 VGPRs at 2, 141 at 4, 256 at 8), the occupancy matters more
-// (round 6) default 1: the tips / filter pass C3 14.3 -> 13.8 ms, C5 50.1 -> 46.0 (4: 61.2);
-// cf.scan_u=2 keeps round 3's two words
-constexpr int kScanUDefault = 1;
+// More words per wave means fewer waves: C3 recount with 1 / 2 / 4 / 8 words 5.5 / 5.7 / 8.3 /
+// 18.0 ms (79 VGPRs at 2, 141 at 4, 256 at 8), the occupancy matters more; the tips / filter
+// pass with one word against round 3's two C3 14.3 -> 13.8 ms, C5 50.1 -> 46.0 (4: 61.2), so one
+// (round 6). The kernels keep their sv[kScanU] array bodies: with plain variables the tips pass
+// measured slower
+constexpr int kScanU = 1;
 
 // A wave's appends to a global id list, staged in LDS and published 64 at a time with one
 // cursor atomic (at C5 the candidates and the peel's branch nodes occur in most waves, and an
@@ -162,7 +163,6 @@ __device__ __forceinline__ uint64_t word_ones(uint64_t w, uint64_t D) {
     return e0 + 64 <= D ? ~0ull : e0 < D ? (~0ull >> (64 - (D - e0))) : 0ull;
 }
 
-template <int kScanU>
 __global__ void __launch_bounds__(kBlock) k_post_filter(GraphView g, uint64_t w_lo, uint64_t w_hi, uint64_t *post,
                                                         unsigned long long *counts, bool fresh) {
     const int lane = threadIdx.x & 63;
@@ -215,7 +215,7 @@ __global__ void __launch_bounds__(kBlock) k_word_pop(const uint64_t *bm, uint64_
 // kFresh: every edge is valid before the filter (mcaat_graph::all_valid), so an edge is a tip
 // iff it has no out-edges at all, and no window of the unfiltered bitmap is read; a template
 // parameter, so that the fresh form keeps none of the other's registers
-template <int kScanU, bool kFresh>
+template <bool kFresh>
 __global__ void __launch_bounds__(kBlock) k_tips_filter(GraphView g, uint64_t w_lo, uint64_t w_hi, uint64_t *tip_bm,
                                                         const uint64_t *post, unsigned long long *counts, PeelArrays pa,
                                                         uint64_t thr, uint64_t *cand, uint64_t cap) {
@@ -363,9 +363,9 @@ __global__ void __launch_bounds__(kBlock) k_peel_init(GraphView g, PeelArrays pa
 // ruler_mask + 1 others) compacted into list with one cursor atomic per 4096-edge tile,
 // branch nodes and removed seeds into blist
 constexpr int kTileJ = 16;  // 64-edge words per wave per tile
+constexpr int kPB = 2;      // edges per thread in flight: C3 2 / 4 / 8 / 16 -> peel 22.8 / 23.3 / 24.3 / 26.0 ms
 // (list / blist hold cap / bcap entries; the cursors count past them, and the driver then
 // runs the pass again with larger lists: it is idempotent)
-template <int kPB>
 __global__ void __launch_bounds__(kBlock) k_peel_prep(uint64_t D, PeelArrays pa, uint64_t ruler_mask, uint64_t *list,
                                                       uint64_t cap, unsigned long long *cursor, uint64_t *blist,
                                                       uint64_t bcap, unsigned long long *bcursor) {
@@ -1411,15 +1411,6 @@ bool verbose() {
     return v;
 }
 
-// a hipcub device call: once for the size of its temporary storage, once with the storage
-template <class F>
-void with_cub_temp(F &&call) {
-    size_t tmp = 0;
-    HIP_OK(call((void *)nullptr, tmp));
-    DevBuf<uint8_t> t(tmp);
-    HIP_OK(call((void *)t.p, tmp));
-}
-
 // the in[i] with flags[i] != 0, i in [0, n), in order, into out; returns their count
 template <class T>
 uint64_t select_flagged(mcaat_ctx *ctx, const T *in, const uint8_t *flags, uint64_t n, T *out) {
@@ -1498,9 +1489,7 @@ static void run_peel(mcaat_graph *g, const uint64_t *seed_bm, PeelState &ps) {
         list.alloc(cap);
         blist.alloc(bcap);
         HIP_OK(hipMemsetAsync(cur.p, 0, cur.bytes(), st));
-        const int64_t pb = knob(ctx, "cf.prep_batch", 2);  // edges per thread in flight: C3 2 / 4 / 8 / 16 -> peel 22.8 / 23.3 / 24.3 / 26.0 ms
-        auto prep = pb == 4 ? k_peel_prep<4> : pb == 8 ? k_peel_prep<8> : pb == 16 ? k_peel_prep<16> : k_peel_prep<2>;
-        launch_at(st, dim3(grid_for(D, kBlock * kTileJ)), dim3(kBlock), prep, D, pa, ruler_mask, list.p, cap, cur.p, blist.p,
+        launch_at(st, dim3(grid_for(D, kBlock * kTileJ)), dim3(kBlock), k_peel_prep, D, pa, ruler_mask, list.p, cap, cur.p, blist.p,
                   bcap, cur.p + 1);
         unsigned long long hc[2];
         HIP_OK(hipMemcpyAsync(hc, cur.p, 16, hipMemcpyDeviceToHost, st));
@@ -2221,7 +2210,6 @@ struct CfRun {
     mcaat_cycles *out;
     // DepthLevelSearch straight from the device list (one GPU; cf.dls_host=1: through the host)
     const bool dev_dls;
-    const int64_t scan_u;  // cf.scan_u: words in flight per wave in the scans (1, 2, 4)
 
     // ---- what crosses a stage boundary: the stage that writes it -> the last one that reads it
     DevBuf<uint64_t> seeds;       // tips before the multiplicity filter (whole graph): tips_filter -> peel
@@ -2242,7 +2230,7 @@ struct CfRun {
         : g(gr), ctx(gr->ctx), st(gr->ctx->stream), comm(c), N(c ? c->world : 1), R(c ? c->rank : 0), D(gr->D),
           nw(gr->n_words()), w_lo(nw * (uint64_t)R / (uint64_t)N), w_hi(nw * (uint64_t)(R + 1) / (uint64_t)N),
           wgrid(grid_for(nw * 64, kBlock, (unsigned)gr->ctx->n_cu * 16)), p(pa), out(res),
-          dev_dls(!c && knob(gr->ctx, "cf.dls_host", 0) == 0), scan_u(knob(gr->ctx, "cf.scan_u", kScanUDefault)) {}
+          dev_dls(!c && knob(gr->ctx, "cf.dls_host", 0) == 0) {}
 
     // bytes of each rank's words of a bitmap (the all-gathers' sizes)
     std::vector<uint64_t> word_bytes() const {
@@ -2319,8 +2307,7 @@ struct CfRun {
         DevBuf<uint64_t> mpost;
         if (comm) mpost.alloc(std::max<uint64_t>(w_hi - w_lo, 1));
         if (w_hi > w_lo) {
-            auto kern = scan_u == 1 ? k_post_filter<1> : scan_u == 4 ? k_post_filter<4> : k_post_filter<2>;
-            launch_at(st, dim3(wgrid), dim3(kBlock), kern, g->view(), w_lo, w_hi, comm ? mpost.p : post.p + w_lo, cnt, fresh);
+            launch_at(st, dim3(wgrid), dim3(kBlock), k_post_filter, g->view(), w_lo, w_hi, comm ? mpost.p : post.p + w_lo, cnt, fresh);
         }
         if (comm) {
             HIP_OK(hipStreamSynchronize(st));
@@ -2355,9 +2342,7 @@ struct CfRun {
         const PeelArrays fa{fuse ? ps.nf.p : nullptr, fuse ? ps.nxk.p : nullptr, nullptr, nullptr, nullptr, nullptr,
                             post.p, ps.wpre, nw};
         if (w_hi > w_lo) {
-            auto kern = scan_u == 1   ? (fresh ? k_tips_filter<1, true> : k_tips_filter<1, false>)
-                        : scan_u == 4 ? (fresh ? k_tips_filter<4, true> : k_tips_filter<4, false>)
-                                      : (fresh ? k_tips_filter<2, true> : k_tips_filter<2, false>);
+            auto kern = fresh ? k_tips_filter<true> : k_tips_filter<false>;
             launch_at(st, dim3(wgrid), dim3(kBlock), kern, g->view(), w_lo, w_hi, my_seeds, post.p, cnt, fa,
                       (uint64_t)p.threshold_multiplicity, clist.p, ccap);
         }
@@ -2509,10 +2494,9 @@ uint64_t graph_valid_out_ranks(const mcaat_graph *g, uint64_t *ids, uint32_t *nb
     hipLaunchKernelGGL(k_word_popc, dim3(grid_for(nw, kBlock, (unsigned)g->ctx->n_cu * 16)), dim3(kBlock), 0, st,
                        (const uint64_t *)g->valid.p, nw, pc.p);
     LAUNCH_OK();
-    size_t tmp = 0;
-    HIP_OK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, pc.p, wpre.p, (size_t)(nw + 1), st));
-    DevBuf<uint8_t> t(tmp);
-    HIP_OK(hipcub::DeviceScan::ExclusiveSum(t.p, tmp, pc.p, wpre.p, (size_t)(nw + 1), st));
+    with_cub_temp([&](void *t, size_t &tmp) {
+        return hipcub::DeviceScan::ExclusiveSum(t, tmp, pc.p, wpre.p, (size_t)(nw + 1), st);
+    });
     uint64_t n = 0;
     d2h(g->ctx, &n, wpre.p + nw, 8);
     if (!ids || !n) return n;

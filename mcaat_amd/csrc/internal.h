@@ -422,6 +422,15 @@ void launch_at(hipStream_t st, dim3 grid, dim3 block, void (*k)(P...), A &&...a)
     LAUNCH_OK();
 }
 
+// a hipcub device call: once for the size of its temporary storage, once with the storage
+template <class F>
+void with_cub_temp(F &&call) {
+    size_t tmp = 0;
+    HIP_OK(call((void *)nullptr, tmp));
+    DevBuf<uint8_t> t(tmp);
+    HIP_OK(call((void *)t.p, tmp));
+}
+
 inline uint64_t next_pow2(uint64_t x) {
     uint64_t p = 1;
     while (p < x) p <<= 1;

@@ -119,6 +119,7 @@ __device__ __forceinline__ uint64_t lower_bound_dir(const uint64_t *key, const u
 // group of any of them, so the first such edge of the group (a local scan around e) writes
 // in_info for every edge of N = target(e) — no search from the random in-group of each edge.
 // Edges of nodes without predecessors keep in_info = 0 (an empty mask).
+// The per-edge form in global memory (sdbg.adj_lds=0): the tests' reference for k_adjacency_own.
 __global__ void __launch_bounds__(kBlock) k_adjacency(const uint64_t *key, uint64_t D, int k, const uint64_t *dir,
                                                       int shift, uint64_t *out_info, uint64_t *in_info) {
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
@@ -147,124 +148,20 @@ __global__ void __launch_bounds__(kBlock) k_adjacency(const uint64_t *key, uint6
     }
 }
 
-// The same for the block's run of kAdjB consecutive edges, with every search and scan in LDS.
-// Sources are sorted, so for each W the targets (W, s[1..k-1]) of the run lie in one key
-// range, bounded by the run's first and last source; the four ranges (~kAdjB/4 keys each)
-// and the run's own keys (with a group-sized halo on each side, for the in-group scans) are
-// loaded once, coalesced. A range larger than cap (skewed key spaces) falls back to the
-// directory search in global memory. The ranges come from k_adj_bounds (one thread per
-// (run, W)), so a run's range and own-key loads go out together: round 2 searched the
-// directory inside the run's workgroup first, a chain of dependent loads per run (C2 30 ms).
-constexpr int kAdjB = 2048;
-constexpr int kAdjT = 1024;   // threads per run: two edges each
-constexpr int kAdjCap = 1024;
-constexpr int kAdjHalo = 16;  // an in-group holds at most 16 edges
-__global__ void __launch_bounds__(kBlock) k_adj_bounds(const uint64_t *key, uint64_t D, int k, const uint64_t *dir,
-                                                       int shift, uint64_t nruns, uint64_t *bounds) {
-    const uint64_t top = (uint64_t)1 << (2 * (k - 1));
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < 4 * nruns; t += stride) {
-        const uint64_t r = t >> 2, W = t & 3;
-        const uint64_t e0 = r * kAdjB, e1 = e0 + kAdjB < D ? e0 + kAdjB : D;
-        const uint64_t a = (W * top) | (key[e0] >> 4), b = (W * top) | (key[e1 - 1] >> 4);
-        const uint64_t lo = lower_bound_dir(key, dir, shift, a << 2);
-        const uint64_t qb = (b + 1) << 2;  // past the key space when b is the last label
-        const uint64_t hi = qb >> (2 * (k + 1)) ? D : lower_bound_dir(key, dir, shift, qb);
-        bounds[8 * r + W] = lo;
-        bounds[8 * r + 4 + W] = hi;
-    }
-}
-
-__global__ void __launch_bounds__(kAdjT) k_adjacency_lds(const uint64_t *key, uint64_t D, int k, const uint64_t *dir,
-                                                         int shift, uint32_t cap, const uint64_t *bounds,
-                                                         uint64_t *out_info, uint64_t *in_info) {
-    __shared__ uint64_t rng[4][kAdjCap];
-    __shared__ uint64_t own[kAdjB + 2 * kAdjHalo];
-    __shared__ uint64_t srlo[4];
-    __shared__ uint32_t srn[4];
-    const uint64_t e0 = (uint64_t)blockIdx.x * kAdjB;
-    if (e0 >= D) return;
-    const uint64_t e1 = e0 + kAdjB < D ? e0 + kAdjB : D;
-    // the run's four ranges (uniform loads), also kept in LDS for the per-edge lookups
-    uint64_t rlo[4];
-    uint32_t rn[4];
-#pragma unroll
-    for (int W = 0; W < 4; ++W) {
-        rlo[W] = bounds[8 * blockIdx.x + W];
-        const uint64_t hi = bounds[8 * blockIdx.x + 4 + W];
-        rn[W] = hi - rlo[W] <= (uint64_t)cap ? (uint32_t)(hi - rlo[W]) : 0xFFFFFFFFu;
-    }
-    if (threadIdx.x < 4) {
-        srlo[threadIdx.x] = rlo[threadIdx.x];
-        srn[threadIdx.x] = rn[threadIdx.x];
-    }
-    // own[j] = key[e0 - kAdjHalo + j]; outside [0, D): a value no group matches
-    const uint64_t olo = e0 >= (uint64_t)kAdjHalo ? e0 - kAdjHalo : 0;
-    const uint32_t opad = (uint32_t)(e0 - olo);  // halo entries actually before e0
-    for (uint32_t j = threadIdx.x; j < kAdjB + 2 * kAdjHalo; j += kAdjT) {
-        const uint64_t x = e0 + j - kAdjHalo;  // wraps below 0 for the first run
-        own[j] = (j >= (uint32_t)kAdjHalo - opad && x < D) ? key[x] : ~0ULL;
-    }
-#pragma unroll
-    for (int W = 0; W < 4; ++W) {
-        const uint32_t n = rn[W];
-        if (n == 0xFFFFFFFFu) continue;
-        for (uint32_t i = threadIdx.x; i < n; i += kAdjT) rng[W][i] = key[rlo[W] + i];
-    }
-    __syncthreads();
-    for (uint64_t e = e0 + threadIdx.x; e < e1; e += kAdjT) {
-        const uint32_t oe = (uint32_t)(e - e0) + kAdjHalo;
-        const uint64_t K = own[oe];
-        const uint64_t W = K & 3, R = K >> 2;
-        const uint64_t Rt = (W << (2 * (k - 1))) | (R >> 2);
-        uint64_t lo;
-        unsigned m = 0;
-        const uint32_t n = srn[W];
-        if (n != 0xFFFFFFFFu) {
-            const uint64_t *r = rng[W];
-            const uint64_t q = Rt << 2;
-            uint32_t a = 0, b = n;
-            while (a < b) {
-                const uint32_t mid = (a + b) >> 1;
-                if (r[mid] < q) a = mid + 1; else b = mid;
-            }
-            lo = srlo[W] + a;
-            // the range holds every key below (last target + 1) << 2: all of Rt's edges
-            for (uint32_t i = a; i < n && (r[i] >> 2) == Rt; ++i) m |= 1u << (r[i] & 3);
-        } else {
-            lo = lower_bound_dir(key, dir, shift, Rt << 2);
-            for (uint64_t i = lo; i < D && (key[i] >> 2) == Rt; ++i) m |= 1u << (key[i] & 3);
-        }
-        out_info[e] = lo | ((uint64_t)m << kIdxBits);
-        if (!m) continue;
-        // e's in-group (labels sharing s[1..k-1], key >> 4) from the staged keys; a group cut
-        // by the halo's edge cannot occur (groups hold at most kAdjHalo edges) except at the
-        // ends of the key array, where the ~0 fill stops the scans
-        const uint64_t gk = K >> 4;
-        uint32_t gs = oe;
-        while (gs > 0 && (own[gs - 1] >> 4) == gk) --gs;
-        unsigned pm = 0;
-        int j = 0;
-        for (uint32_t q = gs; q < (uint32_t)(kAdjB + 2 * kAdjHalo) && (own[q] >> 4) == gk && j < 16; ++q, ++j)
-            if ((own[q] & 3) == W) pm |= 1u << j;
-        if ((uint32_t)(__ffs(pm) - 1) != oe - gs) continue;
-        const uint64_t v = (e0 - kAdjHalo + gs) | ((uint64_t)pm << kIdxBits);
-        const int deg = __popc(m);
-        for (int r = 0; r < deg; ++r) in_info[lo + r] = v;
-    }
-}
-
-// Round 3: in_info written from the owning side, coalesced. Runs start at group boundaries
+// The adjacency (round 3): runs of ~kOwnB consecutive edges, a workgroup each, every search and
+// scan in LDS, in_info written from the owning side, coalesced. Runs start at group boundaries
 // (edges sharing key >> 4; at most 16), so every in-edge of a node sits in one run: the run of
 // the node's writer (the first in-edge of the group with the node's W, as above). Run r owns,
 // for each W, the in_info slots of the targets between its first source and the next run's
 // first source: [O_W(r), O_W(r + 1)) with O_W(r) = lower_bound((W, key[s_r] >> 4) << 2), run 0
 // from the start of the W quarter and the last run to its end, so the owned ranges tile
-// [0, D) and a run's targets (the old per-W search ranges) lie inside its owned ranges. A run
+// [0, D) and a run's targets (per W one key range, its first to its last source's) lie inside them. A run
 // stages the keys of its four owned ranges and their in_info words (zero: no predecessor) in
 // LDS, searches and fills them there, and writes every owned slot once: no clearing pass and
 // no scattered 8-B stores (C2: those cost 7.5 ms of 23 plus the 19-GB clear). A run whose owned
 // ranges exceed the LDS cap clears them in global memory and writes directly (directory search).
+// It superseded round 2's k_adjacency_lds (target ranges in LDS, scattered in_info stores after an
+// 8 D-byte clear; last in 7a50990): sdbg_build C3 39.0 -> 38.5 ms, C2 104.4 -> 100.4.
 constexpr int kOwnT = 1024;               // threads per run
 constexpr int kOwnB = 2048;               // nominal edges per run (its start moves to a group start)
 constexpr int kOwnMax = kOwnB + 16;       // a run holds at most this many edges
@@ -561,12 +458,10 @@ struct LinePlace {
 };
 
 constexpr int kSBlock = 1024;
-// rounds of entries in flight in the level-1/2 scatters (MCAAT_SPF). Measured (round 6, C3):
-// 1 / 2 / 4 rounds: sdbg_build 36.0 / 39.3 / 37.9 ms, so 1 (profiles/r06_c3_msd_prefetch_ab.txt)
-#ifndef MCAAT_SPF
-#define MCAAT_SPF 1
-#endif
-constexpr int kSPF = MCAAT_SPF;
+// rounds of entries in flight in the level-1/2 scatters. Measured (round 6, C3): 1 / 2 / 4
+// rounds: sdbg_build 36.0 / 39.3 / 37.9 ms, so 1 (profiles/r06_c3_msd_prefetch_ab.txt). The
+// scatters keep their na[kSPF] array bodies (the reasoning of kScanU in cycle_finder.hip)
+constexpr int kSPF = 1;
 
 __global__ void __launch_bounds__(kSBlock) k_msd1_scatter(const uint64_t *ckeys, const uint32_t *ccnt, uint64_t n,
                                                           int k, const uint32_t *off, uint64_t *out) {
@@ -1031,7 +926,8 @@ __global__ void __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(OC
 }
 
 // one workgroup per listed level-3 bucket of <= CAP items; larger ones are forwarded to the
-// next list (or flagged when there is none: the caller falls back to the radix sort)
+// next list (or flagged when there is none: the caller falls back to the radix sort). The last
+// stage; as <256, kMidSort> also the mid stage until k_msd3_count (C2 46.8 -> 19.4 ms)
 template <int THREADS, int CAP>
 __global__ void __launch_bounds__(THREADS) k_msd3_block(const uint64_t *in, const uint64_t *off2, const uint64_t *real2,
                                                         const uint64_t *base3, int k, const uint32_t *big, uint64_t nbig,
@@ -1061,167 +957,182 @@ __global__ void __launch_bounds__(THREADS) k_msd3_block(const uint64_t *in, cons
 
 template <class T>
 void excl_scan(hipStream_t st, const T *in, T *out, uint64_t n) {
-    size_t tmp = 0;
-    HIP_OK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, in, out, (size_t)n, st));
-    DevBuf<uint8_t> t(tmp);
-    HIP_OK(hipcub::DeviceScan::ExclusiveSum(t.p, tmp, in, out, (size_t)n, st));
+    with_cub_temp([&](void *t, size_t &tmp) {
+        return hipcub::DeviceScan::ExclusiveSum(t, tmp, in, out, (size_t)n, st);
+    });
 }
 
-// returns false (nothing written) if a bucket exceeds the LDS sorts: caller uses the radix sort
+// a device counter's value on the host; the stream is synchronised
+template <class T>
+T read_counter(hipStream_t st, const T *p) {
+    T h{};
+    HIP_OK(hipMemcpyAsync(&h, p, sizeof(T), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    return h;
+}
+
+constexpr uint64_t NB = (uint64_t)kMS * kMS;  // level-3 buckets
+
+// The n canonical (key, count) entries, which expand to D oriented edges, sorted into key / mult,
+// level by level. Returns false (nothing usable written) if a bucket exceeds the LDS sorts: the
+// caller uses the radix sort. The levels' device buffers are declared in the order the levels
+// allocate them, so they go back to the arena in reverse when the sort ends, apart from the two
+// released early (blk1 after level 1's scatter, l1 after level 2's).
 bool msd_sort(mcaat_ctx *ctx, const uint64_t *ckeys, const uint32_t *ccnt, uint64_t n, int k, uint64_t D,
               uint64_t *key, uint16_t *mult) {
     hipStream_t st = ctx->stream;
-    const uint64_t nch1 = (n + kCh1 - 1) / kCh1;
-    // level 1: per-chunk counts -> per-block line totals -> bucket bases -> chunk run starts
-    const uint64_t nblk1 = (nch1 + kBlkCh - 1) / kBlkCh;
-    DevBuf<uint32_t> cc1(nch1 * kMS ? nch1 * kMS : 1);
-    DevBuf<unsigned long long> blk1(nblk1 * kMS ? nblk1 * kMS : 1), tot1(kMS + 1), base1(kMS + 1);
-    HIP_OK(hipMemsetAsync(blk1.p, 0, blk1.bytes(), st));
-    HIP_OK(hipMemsetAsync(tot1.p, 0, tot1.bytes(), st));
-    hipLaunchKernelGGL(k_msd1_hist, dim3((unsigned)nch1), dim3(kBlock), 0, st, ckeys, ccnt, n, k, cc1.p, blk1.p);
-    LAUNCH_OK();
-    hipLaunchKernelGGL(k_blk_scan, dim3(grid_for(kMS, kBlock)), dim3(kBlock), 0, st, blk1.p, nblk1, (uint64_t)kMS,
-                       tot1.p);
-    LAUNCH_OK();
-    excl_scan(st, (const uint64_t *)tot1.p, (uint64_t *)base1.p, kMS + 1);  // in lines
-    hipLaunchKernelGGL(k_chunk_off, dim3(grid_for(nblk1 * kMS, kBlock)), dim3(kBlock), 0, st, cc1.p, nch1,
-                       (uint64_t)kMS, (const unsigned long long *)blk1.p, (const unsigned long long *)base1.p,
-                       (const uint64_t *)nullptr, (uint64_t)0, 0);
-    LAUNCH_OK();
-    std::vector<uint64_t> off1(kMS + 1);
-    HIP_OK(hipMemcpyAsync(off1.data(), base1.p, 8 * (kMS + 1), hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    for (auto &x : off1) x *= kIL;  // lines -> items
-    DevBuf<uint64_t> l1(off1[kMS] ? off1[kMS] : 1);
-    hipLaunchKernelGGL(k_msd1_scatter, dim3((unsigned)nch1), dim3(kSBlock), 0, st, ckeys, ccnt, n, k,
-                       (const uint32_t *)cc1.p, l1.p);
-    LAUNCH_OK();
-    blk1.release();
-    // level 2: chunks of each level-1 bucket (consecutive), per-chunk sub counts
-    std::vector<uint64_t> cstart, seg_first(kMS + 1);
-    std::vector<uint32_t> clen, cbk;
-    for (int b = 0; b < kMS; ++b) {
-        seg_first[b] = cstart.size();
-        for (uint64_t o = off1[b]; o < off1[b + 1]; o += kCh2) {
-            cstart.push_back(o);
-            clen.push_back((uint32_t)std::min<uint64_t>(kCh2, off1[b + 1] - o));
-            cbk.push_back((uint32_t)b);
-        }
-    }
-    seg_first[kMS] = cstart.size();
-    const uint64_t nch2 = cstart.size(), NB = (uint64_t)kMS * kMS;
-    DevBuf<uint64_t> dcs(nch2 ? nch2 : 1), dseg(kMS + 1);
-    DevBuf<uint32_t> dcl(nch2 ? nch2 : 1), dcb(nch2 ? nch2 : 1), cc2(nch2 * kMS ? nch2 * kMS : 1);
-    DevBuf<unsigned long long> tot2(NB + 1), real2(NB + 1), cur2(NB + 1), base3(NB + 1);
-    HIP_OK(hipMemcpyAsync(dcs.p, cstart.data(), 8 * nch2, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(dcl.p, clen.data(), 4 * nch2, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(dcb.p, cbk.data(), 4 * nch2, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(dseg.p, seg_first.data(), 8 * (kMS + 1), hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemsetAsync(tot2.p, 0, tot2.bytes(), st));
-    HIP_OK(hipMemsetAsync(real2.p, 0, real2.bytes(), st));
-    if (nch2) {
-        hipLaunchKernelGGL(k_msd2_hist, dim3((unsigned)nch2), dim3(kBlock), 0, st, l1.p, dcs.p, dcl.p, dcb.p, k,
-                           tot2.p, real2.p, cc2.p);
-        LAUNCH_OK();
-    }
-    excl_scan(st, (const uint64_t *)tot2.p, (uint64_t *)cur2.p, NB + 1);
-    excl_scan(st, (const uint64_t *)real2.p, (uint64_t *)base3.p, NB + 1);
-    uint64_t n2 = 0, nreal = 0;
-    HIP_OK(hipMemcpyAsync(&n2, cur2.p + NB, 8, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipMemcpyAsync(&nreal, base3.p + NB, 8, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    if (nreal != D) throw Error(MCAAT_E_CAPACITY, "msd_sort: item count mismatch");
-    if (n2 / kIL >= (1ull << 32)) throw Error(MCAAT_E_CAPACITY, "msd_sort: 2^32 or more lines");
-    DevBuf<uint64_t> off2(NB + 1);
-    HIP_OK(hipMemcpyAsync(off2.p, cur2.p, 8 * (NB + 1), hipMemcpyDeviceToDevice, st));
-    DevBuf<uint64_t> l2(n2 ? n2 : 1);
-    if (nch2) {
-        hipLaunchKernelGGL(k_chunk_off, dim3(grid_for(NB, kBlock)), dim3(kBlock), 0, st, cc2.p, nch2, (uint64_t)kMS,
-                           (const unsigned long long *)nullptr, (const unsigned long long *)cur2.p,
-                           (const uint64_t *)dseg.p, (uint64_t)kMS, 1);
-        LAUNCH_OK();
-        hipLaunchKernelGGL(k_msd2_scatter, dim3((unsigned)nch2), dim3(kSBlock), 0, st, l1.p, dcs.p, dcl.p,
-                           (const uint32_t *)cc2.p, k, l2.p);
-        LAUNCH_OK();
-    }
-    l1.release();
+    // level 1
+    DevBuf<uint32_t> cc1;                          // per chunk and bucket: count, then run start (lines)
+    DevBuf<unsigned long long> blk1, tot1, base1;  // lines per block of chunks; per bucket; bucket starts
+    std::vector<uint64_t> off1;                    // bucket starts in l1, in items: level 1 -> 2
+    DevBuf<uint64_t> l1;                           // the items by level-1 bucket: level 1 -> 2
+    // level 2
+    DevBuf<uint64_t> dcs, dseg;                    // chunk starts in l1; each level-1 bucket's first chunk
+    DevBuf<uint32_t> dcl, dcb, cc2;                // chunk lengths, chunk buckets; as cc1
+    // per level-3 bucket: padded items, real items, and the scans of both (real2, base3: level 2 -> 3)
+    DevBuf<unsigned long long> tot2, real2, cur2, base3;
+    DevBuf<uint64_t> off2, l2;                     // bucket starts in l2, the items: level 2 -> 3
     // level 3
-    DevBuf<uint32_t> big(NB);
-    DevBuf<unsigned long long> nbig(1);
-    DevBuf<int> too(1);
-    HIP_OK(hipMemsetAsync(nbig.p, 0, 8, st));
-    HIP_OK(hipMemsetAsync(too.p, 0, 4, st));
-    // 24 KB of LDS per workgroup, 96 registers: five resident per CU
-    hipLaunchKernelGGL(k_msd3_wave, dim3((unsigned)ctx->n_cu * 5), dim3(kL3Waves * 64), 0, st, l2.p, off2.p,
-                       (const uint64_t *)real2.p, (const uint64_t *)base3.p, k, key, mult, big.p, nbig.p,
-                       (uint32_t)std::min<int64_t>(kWaveSort, knob(ctx, "sort.wave_limit", kWaveSort)),
-                       (int)knob(ctx, "sort.l3_counting", 1));
-    LAUNCH_OK();
-    unsigned long long hb = 0;
-    HIP_OK(hipMemcpyAsync(&hb, nbig.p, 8, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    if (hb) {
-        // mid-size buckets (deep graphs: D / 2^22 above the wave limit) by 256-thread
-        // workgroups, many per CU; the rare larger ones by one 1024-thread workgroup each
-        DevBuf<uint32_t> big2(hb);
-        DevBuf<unsigned long long> nbig2(1);
-        HIP_OK(hipMemsetAsync(nbig2.p, 0, 8, st));
-        const uint32_t mid_limit = (uint32_t)std::min<int64_t>(kMidSort, knob(ctx, "sort.mid_limit", kMidSort));
-        // buckets of <= 1024 items by 128-thread workgroups first (12 KB of LDS, two-wave
-        // barriers, eight resident per CU), the larger ones forwarded; by default only where the
-        // average level-3 bucket is small enough for that stage to take most of them (C2: D / 2^22
-        // ~ 570, sdbg_build 97.4 -> 92.8 ms; C5 ~ 935: 152.8 -> 179.6, so not there)
-        const int64_t small_knob = knob(ctx, "sort.small_mid", -1);
-        const bool small = small_knob >= 0 ? small_knob != 0 : D / NB <= 768;
-        if (small && knob(ctx, "sort.mid_counting", 1) && mid_limit >= kSmallMid) {
-            DevBuf<uint32_t> big1(hb);
-            DevBuf<unsigned long long> nbig1(1);
-            HIP_OK(hipMemsetAsync(nbig1.p, 0, 8, st));
-            hipLaunchKernelGGL((k_msd3_count<128, kSmallMid, 4>), dim3((unsigned)std::min<uint64_t>(hb, (uint64_t)ctx->n_cu * 8)),
-                               dim3(128), 0, st, l2.p, off2.p, (const uint64_t *)real2.p, (const uint64_t *)base3.p, k,
-                               big.p, (uint64_t)hb, key, mult, big1.p, nbig1.p,
-                               (uint32_t)std::min<int64_t>(kSmallMid, knob(ctx, "sort.small_limit", kSmallMid)));
-            LAUNCH_OK();
-            HIP_OK(hipMemcpyAsync(&hb, nbig1.p, 8, hipMemcpyDeviceToHost, st));
-            HIP_OK(hipStreamSynchronize(st));
-            HIP_OK(hipMemcpyAsync(big.p, big1.p, 4 * hb, hipMemcpyDeviceToDevice, st));
-        }
-        if (!hb) {
-            // every listed bucket was sorted above
-        } else if (knob(ctx, "sort.mid_counting", 1)) {
-            // 24 KB of LDS per workgroup; the registers (125) allow four per CU (`sort.mid_occ=5`: five, at 96 registers with spills; C2 2 ms slower)
-            if (knob(ctx, "sort.mid_occ", 4) >= 5)
-                hipLaunchKernelGGL((k_msd3_count<256, kMidSort, 5>), dim3((unsigned)std::min<uint64_t>(hb, (uint64_t)ctx->n_cu * 5)),
-                                   dim3(256), 0, st, l2.p, off2.p, (const uint64_t *)real2.p, (const uint64_t *)base3.p, k,
-                                   big.p, (uint64_t)hb, key, mult, big2.p, nbig2.p, mid_limit);
-            else
-                hipLaunchKernelGGL((k_msd3_count<256, kMidSort, 4>), dim3((unsigned)std::min<uint64_t>(hb, (uint64_t)ctx->n_cu * 4)),
-                                   dim3(256), 0, st, l2.p, off2.p, (const uint64_t *)real2.p, (const uint64_t *)base3.p, k,
-                                   big.p, (uint64_t)hb, key, mult, big2.p, nbig2.p, mid_limit);
-        } else {
-            hipLaunchKernelGGL((k_msd3_block<256, kMidSort>), dim3((unsigned)std::min<uint64_t>(hb, (uint64_t)ctx->n_cu * 8)),
-                               dim3(256), 0, st, l2.p, off2.p, (const uint64_t *)real2.p, (const uint64_t *)base3.p, k,
-                               big.p, (uint64_t)hb, key, mult, big2.p, nbig2.p, too.p, mid_limit);
-        }
-        LAUNCH_OK();
-        unsigned long long hb2 = 0;
-        HIP_OK(hipMemcpyAsync(&hb2, nbig2.p, 8, hipMemcpyDeviceToHost, st));
+    DevBuf<uint32_t> big;                          // the buckets above the one-wave limit
+    DevBuf<unsigned long long> nbig;
+    DevBuf<int> too;                               // set by a bucket above every LDS sort
+
+    // level 1: per-chunk counts -> per-block line totals -> bucket bases -> chunk run starts -> scatter
+    auto level1 = [&] {
+        const uint64_t nch1 = (n + kCh1 - 1) / kCh1, nblk1 = (nch1 + kBlkCh - 1) / kBlkCh;
+        cc1.alloc(nch1 * kMS);
+        blk1.alloc(nblk1 * kMS);
+        tot1.alloc(kMS + 1);
+        base1.alloc(kMS + 1);
+        HIP_OK(hipMemsetAsync(blk1.p, 0, blk1.bytes(), st));
+        HIP_OK(hipMemsetAsync(tot1.p, 0, tot1.bytes(), st));
+        launch_at(st, dim3((unsigned)nch1), dim3(kBlock), k_msd1_hist, ckeys, ccnt, n, k, cc1.p, blk1.p);
+        launch_at(st, dim3(grid_for(kMS, kBlock)), dim3(kBlock), k_blk_scan, blk1.p, nblk1, kMS, tot1.p);
+        excl_scan(st, (const uint64_t *)tot1.p, (uint64_t *)base1.p, kMS + 1);  // in lines
+        launch_at(st, dim3(grid_for(nblk1 * kMS, kBlock)), dim3(kBlock), k_chunk_off, cc1.p, nch1, kMS, blk1.p, base1.p,
+                  nullptr, 0, 0);
+        off1.resize(kMS + 1);
+        HIP_OK(hipMemcpyAsync(off1.data(), base1.p, 8 * (kMS + 1), hipMemcpyDeviceToHost, st));
         HIP_OK(hipStreamSynchronize(st));
-        if (hb2) {
-            hipLaunchKernelGGL((k_msd3_block<1024, kBlockSort>), dim3((unsigned)std::min<uint64_t>(hb2, (uint64_t)ctx->n_cu)),
-                               dim3(1024), 0, st, l2.p, off2.p, (const uint64_t *)real2.p, (const uint64_t *)base3.p, k,
-                               big2.p, (uint64_t)hb2, key, mult, (uint32_t *)nullptr,
-                               (unsigned long long *)nullptr, too.p,
-                               (uint32_t)std::min<int64_t>(kBlockSort, knob(ctx, "sort.block_limit", kBlockSort)));
-            LAUNCH_OK();
+        for (auto &x : off1) x *= kIL;  // lines -> items
+        l1.alloc(off1[kMS]);
+        launch_at(st, dim3((unsigned)nch1), dim3(kSBlock), k_msd1_scatter, ckeys, ccnt, n, k, cc1.p, l1.p);
+        blk1.release();
+    };
+
+    // level 2: the chunks of each level-1 bucket (consecutive) -> per-chunk sub counts -> bucket
+    // totals and their scans -> chunk run starts -> scatter
+    auto level2 = [&] {
+        std::vector<uint64_t> cstart, seg_first(kMS + 1);
+        std::vector<uint32_t> clen, cbk;
+        for (int b = 0; b < kMS; ++b) {
+            seg_first[b] = cstart.size();
+            for (uint64_t o = off1[b]; o < off1[b + 1]; o += kCh2) {
+                cstart.push_back(o);
+                clen.push_back((uint32_t)std::min<uint64_t>(kCh2, off1[b + 1] - o));
+                cbk.push_back((uint32_t)b);
+            }
         }
-        int h = 0;
-        HIP_OK(hipMemcpyAsync(&h, too.p, 4, hipMemcpyDeviceToHost, st));
+        seg_first[kMS] = cstart.size();
+        const uint64_t nch2 = cstart.size();
+        dcs.alloc(nch2);
+        dseg.alloc(kMS + 1);
+        dcl.alloc(nch2);
+        dcb.alloc(nch2);
+        cc2.alloc(nch2 * kMS);
+        tot2.alloc(NB + 1);
+        real2.alloc(NB + 1);
+        cur2.alloc(NB + 1);
+        base3.alloc(NB + 1);
+        HIP_OK(hipMemcpyAsync(dcs.p, cstart.data(), 8 * nch2, hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(dcl.p, clen.data(), 4 * nch2, hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(dcb.p, cbk.data(), 4 * nch2, hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(dseg.p, seg_first.data(), 8 * (kMS + 1), hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemsetAsync(tot2.p, 0, tot2.bytes(), st));
+        HIP_OK(hipMemsetAsync(real2.p, 0, real2.bytes(), st));
+        if (nch2)
+            launch_at(st, dim3((unsigned)nch2), dim3(kBlock), k_msd2_hist, l1.p, dcs.p, dcl.p, dcb.p, k, tot2.p, real2.p,
+                      cc2.p);
+        excl_scan(st, (const uint64_t *)tot2.p, (uint64_t *)cur2.p, NB + 1);
+        excl_scan(st, (const uint64_t *)real2.p, (uint64_t *)base3.p, NB + 1);
+        uint64_t n2 = 0, nreal = 0;
+        HIP_OK(hipMemcpyAsync(&n2, cur2.p + NB, 8, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(&nreal, base3.p + NB, 8, hipMemcpyDeviceToHost, st));
         HIP_OK(hipStreamSynchronize(st));
-        if (h) return false;
-    }
-    HIP_OK(hipStreamSynchronize(st));
-    return true;
+        if (nreal != D) throw Error(MCAAT_E_CAPACITY, "msd_sort: item count mismatch");
+        if (n2 / kIL >= (1ull << 32)) throw Error(MCAAT_E_CAPACITY, "msd_sort: 2^32 or more lines");
+        off2.alloc(NB + 1);
+        HIP_OK(hipMemcpyAsync(off2.p, cur2.p, 8 * (NB + 1), hipMemcpyDeviceToDevice, st));
+        l2.alloc(n2);
+        if (nch2) {
+            launch_at(st, dim3(grid_for(NB, kBlock)), dim3(kBlock), k_chunk_off, cc2.p, nch2, kMS, nullptr, cur2.p,
+                      dseg.p, kMS, 1);
+            launch_at(st, dim3((unsigned)nch2), dim3(kSBlock), k_msd2_scatter, l1.p, dcs.p, dcl.p, cc2.p, k, l2.p);
+        }
+        l1.release();
+    };
+
+    // level 3: one wave per bucket up to the wave limit; the larger ones are listed and go through
+    // the small (128 threads), mid (256) and block (1024) stages in turn, each forwarding the
+    // buckets above its limit to the next list. False when a bucket exceeds the last.
+    auto level3 = [&]() -> bool {
+        const uint64_t *real = (const uint64_t *)real2.p, *base = (const uint64_t *)base3.p;
+        auto limit = [&](const char *name, int64_t most) {
+            return (uint32_t)std::min<int64_t>(most, knob(ctx, name, most));
+        };
+        // a stage's workgroups: one per listed bucket, at most per_cu on each CU
+        auto grid = [&](uint64_t listed, int per_cu) {
+            return dim3((unsigned)std::min<uint64_t>(listed, (uint64_t)ctx->n_cu * per_cu));
+        };
+        big.alloc(NB);
+        nbig.alloc(1);
+        too.alloc(1);
+        HIP_OK(hipMemsetAsync(nbig.p, 0, 8, st));
+        HIP_OK(hipMemsetAsync(too.p, 0, 4, st));
+        // 24 KB of LDS per workgroup, 96 registers: five resident per CU
+        launch_at(st, dim3((unsigned)ctx->n_cu * 5), dim3(kL3Waves * 64), k_msd3_wave, l2.p, off2.p, real, base, k, key,
+                  mult, big.p, nbig.p, limit("sort.wave_limit", kWaveSort), knob(ctx, "sort.l3_counting", 1));
+        uint64_t hb = read_counter(st, nbig.p);
+        if (hb) {
+            DevBuf<uint32_t> big2(hb);
+            DevBuf<unsigned long long> nbig2(1);
+            HIP_OK(hipMemsetAsync(nbig2.p, 0, 8, st));
+            const uint32_t mid_limit = limit("sort.mid_limit", kMidSort);
+            // small: buckets of <= 1024 items by 128-thread workgroups first (12 KB of LDS, two-wave
+            // barriers, eight resident per CU); by default only where the average level-3 bucket
+            // is small enough for that stage to take most of them (C2: D / 2^22 ~ 570, sdbg_build
+            // 97.4 -> 92.8 ms; C5 ~ 935: 152.8 -> 179.6, so not there)
+            const int64_t small_knob = knob(ctx, "sort.small_mid", -1);
+            const bool small = small_knob >= 0 ? small_knob != 0 : D / NB <= 768;
+            if (small && mid_limit >= kSmallMid) {
+                DevBuf<uint32_t> big1(hb);
+                DevBuf<unsigned long long> nbig1(1);
+                HIP_OK(hipMemsetAsync(nbig1.p, 0, 8, st));
+                launch_at(st, grid(hb, 8), dim3(128), k_msd3_count<128, kSmallMid, 4>, l2.p, off2.p, real, base, k, big.p,
+                          hb, key, mult, big1.p, nbig1.p, limit("sort.small_limit", kSmallMid));
+                hb = read_counter(st, nbig1.p);
+                HIP_OK(hipMemcpyAsync(big.p, big1.p, 4 * hb, hipMemcpyDeviceToDevice, st));
+            }
+            // mid (deep graphs: D / 2^22 above the wave limit): 256-thread workgroups, 24 KB of LDS, four
+            // per CU by the registers (`sort.mid_occ=5`: five, at 96 registers with spills; C2 2 ms slower)
+            const int occ = knob(ctx, "sort.mid_occ", 4) >= 5 ? 5 : 4;
+            auto mid = occ == 5 ? k_msd3_count<256, kMidSort, 5> : k_msd3_count<256, kMidSort, 4>;
+            if (hb)  // the small stage may have taken every listed bucket
+                launch_at(st, grid(hb, occ), dim3(256), mid, l2.p, off2.p, real, base, k, big.p, hb, key, mult, big2.p,
+                          nbig2.p, mid_limit);
+            // block: the rare larger ones by one 1024-thread workgroup each
+            const uint64_t hb2 = read_counter(st, nbig2.p);
+            if (hb2)
+                launch_at(st, grid(hb2, 1), dim3(1024), k_msd3_block<1024, kBlockSort>, l2.p, off2.p, real, base, k,
+                          big2.p, hb2, key, mult, nullptr, nullptr, too.p, limit("sort.block_limit", kBlockSort));
+            if (read_counter(st, too.p)) return false;
+        }
+        HIP_OK(hipStreamSynchronize(st));
+        return true;
+    };
+    level1();
+    level2();
+    return level3();
 }
 
 }  // namespace
@@ -1233,15 +1144,10 @@ void sdbg_build(mcaat_ctx *ctx, CountResult &c, int k, mcaat_graph *g) {
     g->k = k;
     DevBuf<unsigned long long> npal(1);
     HIP_OK(hipMemsetAsync(npal.p, 0, 8, st));
-    if (c.n) {
-        hipLaunchKernelGGL(k_count_pal, dim3(grid_for(c.n, kBlock, (unsigned)ctx->n_cu * 16)), dim3(kBlock), 0, st,
-                           c.keys.p, c.n, k, npal.p);
-        LAUNCH_OK();
-    }
-    unsigned long long n_pal = 0;
-    HIP_OK(hipMemcpyAsync(&n_pal, npal.p, 8, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    const uint64_t D = n2 - n_pal;
+    if (c.n)
+        launch_at(st, dim3(grid_for(c.n, kBlock, (unsigned)ctx->n_cu * 16)), dim3(kBlock), k_count_pal, c.keys.p, c.n, k,
+                  npal.p);
+    const uint64_t D = n2 - read_counter(st, npal.p);
     g->D = D;
     g->key.alloc(D ? D : 1);
     g->mult.alloc(mcaat_graph::mult_entries(D));
@@ -1258,15 +1164,13 @@ void sdbg_build(mcaat_ctx *ctx, CountResult &c, int k, mcaat_graph *g) {
         DevBuf<uint64_t> ek(n2);
         DevBuf<uint16_t> em(n2);
         HIP_OK(hipMemsetAsync(npal.p, 0, 8, st));
-        hipLaunchKernelGGL(k_expand, dim3(grid_for(c.n, kBlock)), dim3(kBlock), 0, st, c.keys.p, c.counts.p, c.n, k,
-                           ek.p, em.p, npal.p);
-        LAUNCH_OK();
+        launch_at(st, dim3(grid_for(c.n, kBlock)), dim3(kBlock), k_expand, c.keys.p, c.counts.p, c.n, k, ek.p, em.p,
+                  npal.p);
         DevBuf<uint64_t> sk(n2);
         DevBuf<uint16_t> sm(n2);
-        size_t tmp = 0;
-        HIP_OK(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp, ek.p, sk.p, em.p, sm.p, (size_t)n2, 0, 2 * E + 1, st));
-        DevBuf<uint8_t> t(tmp);
-        HIP_OK(hipcub::DeviceRadixSort::SortPairs(t.p, tmp, ek.p, sk.p, em.p, sm.p, (size_t)n2, 0, 2 * E + 1, st));
+        with_cub_temp([&](void *t, size_t &tmp) {
+            return hipcub::DeviceRadixSort::SortPairs(t, tmp, ek.p, sk.p, em.p, sm.p, (size_t)n2, 0, 2 * E + 1, st);
+        });
         // palindromes left sentinels (1 << 2E) at the end
         if (D) {
             HIP_OK(hipMemcpyAsync(g->key.p, sk.p, 8 * D, hipMemcpyDeviceToDevice, st));
@@ -1301,53 +1205,43 @@ void sdbg_finish(mcaat_ctx *ctx, mcaat_graph *g) {
         DevBuf<int> bad(1);
         HIP_OK(hipMemsetAsync(bad.p, 0, sizeof(int), st));
         const uint64_t key_lim = E >= 32 ? ~0ULL : 1ULL << (2 * E);
-        hipLaunchKernelGGL(k_dir, dim3(grid_for((D + kDirU) / kDirU, kBlock, (unsigned)ctx->n_cu * 16)), dim3(kBlock), 0,
-                           st, g->key.p, D, shift, nprefix, key_lim, dir.p, bad.p);
-        LAUNCH_OK();
+        launch_at(st, dim3(grid_for((D + kDirU) / kDirU, kBlock, (unsigned)ctx->n_cu * 16)), dim3(kBlock), k_dir, g->key.p, D,
+                  shift, nprefix, key_lim, dir.p, bad.p);
         int hb = 0;
         d2h(ctx, &hb, bad.p, sizeof(int));
         if (hb) throw Error(MCAAT_E_INVALID, "sdbg: edge keys are not strictly ascending below 4^(k+1)");
     }
+
+    // adjacency words
     g->out_info.alloc(D);
     g->in_info.alloc(D);
     if (D) {
         KernelTimer kt(ctx, "adjacency", 32.0 * (double)D);  // key read, in_info cleared, two words written
-        // one edge per lane: neighbouring lanes search neighbouring key ranges, so the
-        // searches' loads share lines across the wave (a thread-per-run merge walk that
-        // loses this was 5x slower)
-        const int64_t adj = knob(ctx, "sdbg.adj_lds", 1);  // 1: owner-side runs, 2: round-2 LDS runs, 0: global search
-        if (adj == 1) {
-            const uint32_t cap = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(kOwnCap, knob(ctx, "sdbg.adj_cap", kOwnCap)));
+        if (knob(ctx, "sdbg.adj_lds", 1) != 0) {
+            // group-aligned runs that own their in_info slots (k_adjacency_own)
+            const uint32_t cap = (uint32_t)knob_clamped(ctx, "sdbg.adj_cap", kOwnCap, 0, kOwnCap);
             const uint64_t nruns = (D + kOwnB - 1) / kOwnB;
             DevBuf<uint64_t> bounds(5 * (nruns + 1));
-            hipLaunchKernelGGL(k_own_bounds, dim3(grid_for(nruns + 1, kBlock)), dim3(kBlock), 0, st, g->key.p, D, k,
-                               dir.p, shift, nruns, bounds.p);
-            LAUNCH_OK();
-            hipLaunchKernelGGL(k_adjacency_own, dim3((unsigned)nruns), dim3(kOwnT), 0, st, g->key.p, D, k, dir.p, shift,
-                               cap, (const uint64_t *)bounds.p, g->out_info.p, g->in_info.p);
-        } else if (adj == 2) {
-            HIP_OK(hipMemsetAsync(g->in_info.p, 0, 8 * D, st));
-            const uint32_t cap = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(kAdjCap, knob(ctx, "sdbg.adj_cap", kAdjCap)));
-            const uint64_t nruns = (D + kAdjB - 1) / kAdjB;
-            DevBuf<uint64_t> bounds(8 * nruns);
-            hipLaunchKernelGGL(k_adj_bounds, dim3(grid_for(4 * nruns, kBlock, (unsigned)ctx->n_cu * 16)), dim3(kBlock), 0,
-                               st, g->key.p, D, k, dir.p, shift, nruns, bounds.p);
-            LAUNCH_OK();
-            hipLaunchKernelGGL(k_adjacency_lds, dim3((unsigned)nruns), dim3(kAdjT), 0, st, g->key.p, D, k, dir.p, shift,
-                               cap, (const uint64_t *)bounds.p, g->out_info.p, g->in_info.p);
+            launch_at(st, dim3(grid_for(nruns + 1, kBlock)), dim3(kBlock), k_own_bounds, g->key.p, D, k, dir.p, shift, nruns,
+                      bounds.p);
+            launch_at(st, dim3((unsigned)nruns), dim3(kOwnT), k_adjacency_own, g->key.p, D, k, dir.p, shift, cap, bounds.p,
+                      g->out_info.p, g->in_info.p);
         } else {
+            // sdbg.adj_lds=0, the tests' reference: one edge per lane in global memory (neighbouring
+            // lanes search neighbouring key ranges, so the searches' loads share lines across the
+            // wave; a thread-per-run merge walk that loses this was 5x slower)
             HIP_OK(hipMemsetAsync(g->in_info.p, 0, 8 * D, st));
-            hipLaunchKernelGGL(k_adjacency, dim3(grid_for(D, kBlock)), dim3(kBlock), 0, st, g->key.p, D, k, dir.p,
-                               shift, g->out_info.p, g->in_info.p);
+            launch_at(st, dim3(grid_for(D, kBlock)), dim3(kBlock), k_adjacency, g->key.p, D, k, dir.p, shift, g->out_info.p,
+                      g->in_info.p);
         }
-        LAUNCH_OK();
         kt.stop();
     }
+
+    // valid bitmap: every edge
     g->valid.alloc(mcaat_graph::bitmap_words(D));
     HIP_OK(hipMemsetAsync(g->valid.p + (D + 63) / 64, 0, 8, st));  // the padding word
-    hipLaunchKernelGGL(k_valid_init, dim3(grid_for((D + 63) / 64, kBlock)), dim3(kBlock), 0, st, g->valid.p, D);
+    launch_at(st, dim3(grid_for((D + 63) / 64, kBlock)), dim3(kBlock), k_valid_init, g->valid.p, D);
     g->all_valid = true;
-    LAUNCH_OK();
     HIP_OK(hipStreamSynchronize(st));
 }
 

@@ -67,16 +67,11 @@ KNOBS = {
     "split_eight_ways_big": {"nc.split_first": 3, "nc.big_table": 1, "nc.edge_cap": 300},
     # level-3 buckets through the 256-thread LDS sort, the 1024-thread one, and the radix fallback
     "sort_mid": {"sort.msd": 1, "sort.wave_limit": 0},
-    "sort_mid_bitonic": {"sort.msd": 1, "sort.wave_limit": 0, "sort.mid_counting": 0},
     "sort_mid_occ5": {"sort.msd": 1, "sort.wave_limit": 0, "sort.mid_occ": 5},
     # the 128-thread level-3 stage forwarding everything to the 256-thread one, and skipped
     "sort_small_fwd": {"sort.msd": 1, "sort.wave_limit": 0, "sort.small_mid": 1, "sort.small_limit": 0},
     "sort_small_on": {"sort.msd": 1, "sort.wave_limit": 0, "sort.small_mid": 1},
     "sort_small_off": {"sort.msd": 1, "sort.wave_limit": 0, "sort.small_mid": 0},
-    # the scans with four 64-edge words in flight per wave, the peel prep with eight edges
-    "scan_u4_prep8": {"cf.scan_u": 4, "cf.prep_batch": 8},
-    "scan_u1_prep16": {"cf.scan_u": 1, "cf.prep_batch": 16},
-    "scan_u2": {"cf.scan_u": 2},  # (round 6: 1 is the default, 2 round 3's)
     # DepthLevelSearch with one search per wave and with a full wave of them
     "dls_lanes1": {"cf.dls_lanes": 1},
     "dls_lanes64": {"cf.dls_lanes": 64, "cf.dls_stack": 1, "cf.dls_visited": 2, "cf.dls_lds": 0},
@@ -117,7 +112,8 @@ KNOBS = {
     "nc_no_overlap": {"nc.overlap": 0, "nc.group_budget": 1 << 14},
     # adjacency: per-edge global directory searches; the owner-side runs (default) with every
     # run (cap 0) or the runs whose owned ranges exceed 1500 slots sent to their global
-    # fallback; the round-2 LDS-range kernel, alone and with its ranges over 200 keys in global
+    # fallback; sdbg.adj_lds=2 chose the round-2 kernel until it was retired and, like any other
+    # value, now means the default: alone, and with the runs over 200 owned slots in global
     "adj_global": {"sdbg.adj_lds": 0},
     "adj_cap0": {"sdbg.adj_cap": 0},
     "adj_cap1500": {"sdbg.adj_cap": 1500},
@@ -191,14 +187,16 @@ def test_forced_branches_really_taken(gpu_ctx):
 
 
 def test_retired_knobs_are_unknown(gpu_ctx):
-    """The CycleFinder knobs whose paths are gone answer MCAAT_E_INVALID (-1) like any unknown
-    name; a surviving knob is still accepted."""
-    for name in ("cf.pull_flags", "cf.recount", "cf.walk_budget", "cf.dls_persist"):
+    """The knobs whose paths are gone answer MCAAT_E_INVALID (-1) like any unknown name; a
+    surviving knob is still accepted, the two test handles on live sdbg_build paths among them."""
+    for name in ("cf.pull_flags", "cf.recount", "cf.walk_budget", "cf.dls_persist", "cf.scan_u", "cf.prep_batch",
+                 "sort.mid_counting"):
         with pytest.raises(M.McaatError) as err:
             gpu_ctx.set_knob(name, 1)
         assert err.value.code == -1, name
-    gpu_ctx.set_knob("cf.compact", 1)
-    gpu_ctx.set_knob("cf.compact", -1)  # back to the default
+    for name in ("cf.compact", "sdbg.adj_lds", "sort.l3_counting"):
+        gpu_ctx.set_knob(name, 1)
+        gpu_ctx.set_knob(name, -1)  # back to the default
 
 
 # ---- coverage-matched samples of the bench configs ----------------------------------
@@ -356,14 +354,14 @@ def test_full_size_graph_properties(gpu_ctx, name):
 def test_adjacency_modes_agree_on_every_edge(gpu_ctx, spec_k):
     """The owner-side adjacency (runs starting at group starts, in_info written once per owned
     slot) answers every edge's in- and out-neighbour query exactly like the per-edge global
-    search and the round-2 LDS-range kernel, with and without its LDS staging, including
-    k = 15 (short keys: the directory covers the whole key space) and k = 29."""
+    search, with and without its LDS staging, including k = 15 (short keys: the directory covers
+    the whole key space) and k = 29."""
     name, k_over = spec_k
     spec, k, _ = CASES[name]
     k = k_over or k
     reads = M.Reads.synth(gpu_ctx, spec)
     ref = None
-    for knobs in ({"sdbg.adj_lds": 0}, {"sdbg.adj_lds": 2}, {}, {"sdbg.adj_cap": 0}, {"sdbg.adj_cap": 700}):
+    for knobs in ({"sdbg.adj_lds": 0}, {}, {"sdbg.adj_cap": 0}, {"sdbg.adj_cap": 700}):
         with gpu_ctx.knobs(**{n.replace(".", "__"): v for n, v in knobs.items()}):
             g = M.Graph.build(gpu_ctx, reads, k)
             ids = np.arange(g.size, dtype=np.uint64)
