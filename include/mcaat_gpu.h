@@ -362,7 +362,8 @@ void mcaat_reset_timing(mcaat_ctx *ctx);
  *   nc.free_sync       1: synchronise the stream before the count output's early regrowth frees
  *                      its old buffers (round 4's guard; default 0: the arena's stream order)
  *   nc.ahead           0: ignore mcaat_count_ahead (pass A after the read, default 1)
- *   sort.msd          0: radix sort only, 1: MSD sort whenever k <= 28 (default: D >= 2^16)
+ *   sort.msd          0: radix sort only, 1: MSD sort whenever 5 <= k <= 28 (default: D >= 2^16;
+ *                      below k = 5 a key is shorter than one 11-bit MSD level: always radix)
  *   sort.wave_limit / sort.mid_limit / sort.block_limit   level-3 bucket size limits of the
  *                      one-wave, 256-thread and 1024-thread LDS sorts (above the last: radix)
  *   sort.l3_counting   0: one-wave level-3 buckets by the bitonic network only (default 1: LDS

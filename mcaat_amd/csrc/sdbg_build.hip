@@ -652,6 +652,8 @@ __global__ void __launch_bounds__(kL3Waves * 64) __attribute__((amdgpu_waves_per
     uint32_t *cnt = sc[wave];
     const int E = k + 1;
     const int rb = 2 * E - 2 * kMB;  // key bits below the two MSD levels (item bits 16 .. 16 + rb)
+    // k <= 9: rb < 0 (>= -10), harmless: level 2's digit then holds the whole remainder, so a bucket has
+    // at most one real item; lgb = 6 <= (uint32_t)rb and the bin shift 16 + rb - 6 stays within 0 .. 8
     const uint64_t nb = (uint64_t)kMS * kMS;
     const uint64_t bstride = (uint64_t)gridDim.x * kL3Waves;
     constexpr int NL = 10;  // loads per lane: buckets of up to 640 padded items
@@ -833,7 +835,9 @@ __global__ void __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(OC
         uint32_t lgb = 0;
         while ((1u << lgb) < (uint32_t)THREADS) ++lgb;  // at least one bin per thread
         while ((1u << lgb) < nreal) ++lgb;
-        const bool counting = lgb <= (uint32_t)rb;
+        // signed: rb < 0 at k <= 9 (one real item per bucket, reached only with sort.wave_limit=0), where
+        // lgb >= 7 would make the bin shift 16 + rb - lgb negative at k = 5: the bitonic path takes those
+        const bool counting = (int)lgb <= rb;
         const uint32_t nbins = 1u << lgb, per = nbins / THREADS, sh = counting ? 16 + rb - lgb : 0;
         lds_barrier();  // B1: every thread is past the previous bucket (o and cnt free)
         if (counting)
@@ -1154,8 +1158,11 @@ void sdbg_build(mcaat_ctx *ctx, CountResult &c, int k, mcaat_graph *g) {
     // MSD sort with LDS bucket sorts (k <= 28: key remainder and mult share one word);
     // the radix sort otherwise, or when a bucket is too skewed for LDS
     bool done = false;
-    const int64_t msd = knob(ctx, "sort.msd", -1);  // test knob: 0 never, 1 whenever k <= 28
-    if (k <= 28 && msd != 0 && (D >= (1u << 16) || (msd == 1 && D > 0))) {
+    // test knob: 0 never, 1 whenever 5 <= k <= 28. Below k = 5 a key has fewer than kMB bits
+    // (2(k+1) < 11): level 1's remainder width would be negative, so the radix sort takes those
+    // even when forced (the default never gets there: such a graph has at most 4^5 edges)
+    const int64_t msd = knob(ctx, "sort.msd", -1);
+    if (k <= 28 && 2 * E >= kMB && msd != 0 && (D >= (1u << 16) || (msd == 1 && D > 0))) {
         KernelTimer kt(ctx, "edge_sort", 64.0 * (double)D);
         done = msd_sort(ctx, c.keys.p, c.counts.p, c.n, k, D, g->key.p, g->mult.p);
         kt.stop();
