@@ -368,8 +368,6 @@ void mcaat_reset_timing(mcaat_ctx *ctx);
  *                      one-wave, 256-thread and 1024-thread LDS sorts (above the last: radix)
  *   sort.l3_counting   0: one-wave level-3 buckets by the bitonic network only (default 1: LDS
  *                      counting sort by the next key bits, bitonic for clustered buckets)
- *   sort.mid_occ       5: the 256-thread level-3 counting sort at five workgroups per CU
- *                      (default 4)
  *   sort.small_mid     1: a 128-thread counting-sort stage for level-3 buckets of up to 1024
  *                      items before the 256-thread one, 0: none (default: when D / 2^22 <= 768)
  *   sort.small_limit   largest bucket that stage sorts (default and maximum 1024; larger ones

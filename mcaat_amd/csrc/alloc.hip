@@ -270,13 +270,12 @@ void *dev_alloc(size_t bytes) {
         chunk = (bytes + g - 1) / g * g;
     }
     void *raw = nullptr;
-    static const bool verbose = getenv("MCAAT_VERBOSE") && getenv("MCAAT_VERBOSE")[0] == '1';
-    if (verbose) fprintf(stderr, "[mcaat] arena: new chunk of %zu MiB for a %zu MiB request\n", chunk >> 20, bytes >> 20);
+    if (verbose()) fprintf(stderr, "[mcaat] arena: new chunk of %zu MiB for a %zu MiB request\n", chunk >> 20, bytes >> 20);
     hipError_t e = hipMalloc(&raw, chunk);
     if (e != hipSuccess) {
         (void)hipGetLastError();
         (void)hipDeviceSynchronize();
-        if (verbose) fprintf(stderr, "[mcaat] arena: hipMalloc failed, trimming free chunks\n");
+        if (verbose()) fprintf(stderr, "[mcaat] arena: hipMalloc failed, trimming free chunks\n");
         a.retire();
         a.trim();
         chunk = bytes;
@@ -339,16 +338,14 @@ void arena_check(mcaat_ctx *ctx, int64_t *out) {
     {
         DevBuf<uint64_t> a(n);
         first = a.p;
-        hipLaunchKernelGGL(k_arena_fill, dim3(256), dim3(256), 0, ctx->stream, a.p, n, 1ull, spin);
-        LAUNCH_OK();
+        launch_at(ctx->stream, dim3(256), dim3(256), k_arena_fill, a.p, n, 1ull, spin);
     }  // freed while the slow fill is still queued
     DevBuf<uint64_t> b;
     {
         AllocStreamScope scope(ctx->side);
         b.alloc(n);
     }
-    hipLaunchKernelGGL(k_arena_fill, dim3(256), dim3(256), 0, ctx->side, b.p, n, 2ull, 0ull);
-    LAUNCH_OK();
+    launch_at(ctx->side, dim3(256), dim3(256), k_arena_fill, b.p, n, 2ull, 0ull);
     HIP_OK(hipStreamSynchronize(ctx->side));
     HIP_OK(hipStreamSynchronize(ctx->stream));
     std::vector<uint64_t> h(n);
@@ -367,8 +364,7 @@ void arena_check(mcaat_ctx *ctx, int64_t *out) {
     {
         DevBuf<uint64_t> a(n);
         first = a.p;
-        hipLaunchKernelGGL(k_arena_fill, dim3(256), dim3(256), 0, ctx->stream, a.p, n, 1ull, spin);
-        LAUNCH_OK();
+        launch_at(ctx->stream, dim3(256), dim3(256), k_arena_fill, a.p, n, 1ull, spin);
     }
     hipStream_t fs = nullptr;
     HIP_OK(hipStreamCreateWithFlags(&fs, hipStreamNonBlocking));
@@ -377,11 +373,15 @@ void arena_check(mcaat_ctx *ctx, int64_t *out) {
         AllocStreamScope scope(nullptr);
         c.alloc(n);
     }
-    hipLaunchKernelGGL(k_arena_fill, dim3(256), dim3(256), 0, fs, c.p, n, 3ull, 0ull);
-    const hipError_t le = hipGetLastError();
+    std::exception_ptr le;  // a failed launch is reported once the stream is gone
+    try {
+        launch_at(fs, dim3(256), dim3(256), k_arena_fill, c.p, n, 3ull, 0ull);
+    } catch (...) {
+        le = std::current_exception();
+    }
     (void)hipStreamSynchronize(fs);
     (void)hipStreamDestroy(fs);
-    if (le != hipSuccess) throw Error(MCAAT_E_HIP, std::string("arena check launch: ") + hipGetErrorString(le));
+    if (le) std::rethrow_exception(le);
     HIP_OK(hipStreamSynchronize(ctx->stream));
     HIP_OK(hipMemcpy(h.data(), c.p, 8 * n, hipMemcpyDeviceToHost));
     bool all3 = true;

@@ -328,12 +328,9 @@ void synth_reads(mcaat_ctx *ctx, const mcaat_synth_spec &s, mcaat_reads *out, ui
     out->packed.alloc(out->n_words + 16);
     out->offsets.alloc(s.n_reads + 1);
     HIP_OK(hipMemsetAsync(out->packed.p, 0, out->packed.bytes(), st));
-    hipLaunchKernelGGL(k_synth, dim3(grid_for(out->n_words, kBlock)), dim3(kBlock), 0, st, s, dg.p, out->packed.p,
-                       out->n_words, first, count);
-    LAUNCH_OK();
-    hipLaunchKernelGGL(k_fixed_offsets, dim3(grid_for(count + 1, kBlock)), dim3(kBlock), 0, st,
-                       out->offsets.p, count, (uint64_t)s.read_len);
-    LAUNCH_OK();
+    launch_at(st, dim3(grid_for(out->n_words, kBlock)), dim3(kBlock), k_synth, s, dg.p, out->packed.p, out->n_words, first,
+              count);
+    launch_at(st, dim3(grid_for(count + 1, kBlock)), dim3(kBlock), k_fixed_offsets, out->offsets.p, count, s.read_len);
     HIP_OK(hipStreamSynchronize(st));
 }
 
@@ -1094,7 +1091,7 @@ int mcaat_set_knob(mcaat_ctx *ctx, const char *name, int64_t value) {
         "sort.block_limit", "cf.dls_stack",      "cf.dls_visited", "cf.fc_lock", "cf.fc_relax",
         "cf.fc_out",       "cf.fc_window",       "sdbg.adj_lds",   "sdbg.adj_cap",       "cf.ruler_mask",
         "nc.overlap",      "sort.l3_counting",   "cf.peel_list_div", "cf.peel_list_cap", "cf.cand_cap",
-        "fq.hostpack",     "nc.big_table", "cf.fused_init", "sort.mid_occ", "cf.dls_lanes", "dist.oriented",
+        "fq.hostpack",     "nc.big_table", "cf.fused_init", "cf.dls_lanes", "dist.oriented",
         "sort.small_mid", "sort.small_limit", "cf.dls_host",
         "dist.desc",      "cf.compact",         "cf.fresh",   "nc.split_first", "nc.split_max", "cf.dls_budget", "nc.grow_early",
         "nc.free_sync", "dist.shard_cf", "dist.ruler_mask", "dist.adj_chunk", "dist.dir_edges", "nc.ahead", "dist.adj_ranges", "dist.win_ranges", "cf.dls_lds", "cf.dls_lds_cap", "dist.segs_at_one", "nc.a_mini", "nc.a_adapt", "nc.a_stats", "dist.bfs_sync", "cf.compact_pct", "dist.bfs_block", "dist.bfs_frontier", "dist.res_fixed", "dist.res_batch", "dist.res_block_mb", "dist.walk_block", "dist.walk_batch", "dist.grid_blocks", "dist.preagg"};

@@ -22,6 +22,7 @@
 #include <unordered_set>
 
 #include "comm.h"
+#include "cub_helpers.h"
 
 namespace mcaat {
 
@@ -1399,18 +1400,6 @@ __global__ void k_unpack_bits(const uint64_t *bm, uint64_t D, uint8_t *out) {
     for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < D; e += stride) out[e] = bit_get(bm, e);
 }
 
-unsigned long long read_counter(mcaat_ctx *ctx, unsigned long long *d) {
-    unsigned long long h = 0;
-    HIP_OK(hipMemcpyAsync(&h, d, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_OK(hipStreamSynchronize(ctx->stream));
-    return h;
-}
-
-bool verbose() {
-    static const bool v = getenv("MCAAT_VERBOSE") && getenv("MCAAT_VERBOSE")[0] == '1';
-    return v;
-}
-
 // the in[i] with flags[i] != 0, i in [0, n), in order, into out; returns their count
 template <class T>
 uint64_t select_flagged(mcaat_ctx *ctx, const T *in, const uint8_t *flags, uint64_t n, T *out) {
@@ -1418,7 +1407,7 @@ uint64_t select_flagged(mcaat_ctx *ctx, const T *in, const uint8_t *flags, uint6
     with_cub_temp([&](void *t, size_t &tmp) {
         return hipcub::DeviceSelect::Flagged(t, tmp, in, flags, out, num.p, (size_t)n, ctx->stream);
     });
-    return read_counter(ctx, num.p);
+    return read_counter(ctx->stream, num.p);
 }
 
 // edge ids (bits 0..40) in ascending order, sorted on the device (the append order of a list is
@@ -1510,22 +1499,17 @@ static void run_peel(mcaat_graph *g, const uint64_t *seed_bm, PeelState &ps) {
         HIP_OK(hipMemsetAsync(sowner.p, 0xFF, 4 * nr, st));
         DevBuf<uint32_t> slist(nr);
         launch_at(st, dim3(grid_for(nr, kBlock)), dim3(kBlock), k_peel_super, pa, list.p, nr, slist.p, cur.p + 2);
-        const uint64_t ns = read_counter(ctx, cur.p + 2);
+        const uint64_t ns = read_counter(st, cur.p + 2);
         int rounds = 2;
         while ((1ULL << rounds) < ns + 1) ++rounds;
         rounds += 1;
         // log2(ns)+1 rounds bound the chain depth; most inputs converge far earlier, which
         // a round without changes proves (checked from the fourth round on)
         DevBuf<int> chg(1);
-        int hchg = 1;
         for (int r = 0; ns && r < rounds; ++r) {
             if (r >= 4) HIP_OK(hipMemsetAsync(chg.p, 0, 4, st));
             launch_at(st, dim3(grid_for(ns, kBlock)), dim3(kBlock), k_peel_jump, pa, slist.p, ns, chg.p);
-            if (r >= 4) {
-                HIP_OK(hipMemcpyAsync(&hchg, chg.p, 4, hipMemcpyDeviceToHost, st));
-                HIP_OK(hipStreamSynchronize(st));
-                if (!hchg) break;
-            }
+            if (r >= 4 && !read_counter(st, chg.p)) break;
         }
         launch_at(st, dim3(grid_for(nr, kBlock)), dim3(kBlock), k_peel_final, pa, nr);
     }
@@ -1533,10 +1517,7 @@ static void run_peel(mcaat_graph *g, const uint64_t *seed_bm, PeelState &ps) {
     for (uint64_t it = 0; nb && it < D + 1; ++it) {
         HIP_OK(hipMemsetAsync(changed.p, 0, 4, st));
         launch_at(st, dim3(grid_for(nb, kBlock)), dim3(kBlock), k_peel_branch, v, pa, blist.p, nb, changed.p);
-        int h = 0;
-        HIP_OK(hipMemcpyAsync(&h, changed.p, 4, hipMemcpyDeviceToHost, st));
-        HIP_OK(hipStreamSynchronize(st));
-        if (!h) break;
+        if (!read_counter(st, changed.p)) break;
     }
     // resolution reads valid bits (dev_outgoing), so removal waits until it is complete
     if (nb) launch_at(st, dim3(grid_for(nb, kBlock)), dim3(kBlock), k_peel_apply_list, v, pa, blist.p, nb);
@@ -1894,9 +1875,7 @@ struct FcRunner {
             HIP_OK(hipMemcpyAsync(djs.p, js.data(), 4 * js.size(), hipMemcpyHostToDevice, st));
             launch_at(st, dim3((unsigned)jm.size()), dim3(64), k_fc_conf, r.scratch.p, r.pa, caps.CL, djm.p, djs.p, jm.size(),
                       hkeys.p, hvals.p, hcap, dfirst.p);
-            unsigned int h = none;
-            HIP_OK(hipMemcpyAsync(&h, dfirst.p, 4, hipMemcpyDeviceToHost, st));
-            HIP_OK(hipStreamSynchronize(st));
+            const unsigned int h = read_counter(st, dfirst.p);
             if (h != none) my_first = h;
         }
         verbose_mark(g->ctx, "fc.commit_conf");
@@ -1943,9 +1922,8 @@ struct FcRunner {
         HIP_OK(hipMemcpyAsync(r.dst.p, ls.data(), 8 * Wl, hipMemcpyHostToDevice, st));
         // one search per one-wave workgroup (more searches per wave serialise each
         // other's divergent branches: measured 64 per wave 93 ms, 16: 44, 4: 30, 1: 23 at C3)
-        hipLaunchKernelGGL(k_findcycle, dim3((unsigned)Wl), dim3(64), fc_lds_bytes(caps), st, g->view(), dvis.p, r.dst.p, Wl,
-                           caps, prm, (uint64_t *)r.scratch.p, r.dstat.p);
-        LAUNCH_OK();
+        launch_lds(st, dim3((unsigned)Wl), dim3(64), fc_lds_bytes(caps), k_findcycle, g->view(), dvis.p, r.dst.p, Wl, caps, prm,
+                   (uint64_t *)r.scratch.p, r.dstat.p);
         d2h(g->ctx, r.mine.st.data(), r.dstat.p, Wl * sizeof(FcStatus));
     }
 
@@ -2258,9 +2236,7 @@ struct CfRun {
             wpre.alloc(nw + 1);
             HIP_OK(hipMemsetAsync(pc.p + nw, 0, 4, st));
             launch_at(st, dim3(grid_for(nw, kBlock, (unsigned)ctx->n_cu * 16)), dim3(kBlock), k_word_pop, post.p, nw, pc.p);
-            with_cub_temp([&](void *t, size_t &tmp) {
-                return hipcub::DeviceScan::ExclusiveSum(t, tmp, pc.p, wpre.p, (size_t)(nw + 1), st);
-            });
+            excl_scan(st, pc.p, wpre.p, nw + 1);
             uint32_t slots = 0;
             d2h(ctx, &slots, wpre.p + nw, 4);
             ps.post = post.p;
@@ -2370,7 +2346,7 @@ struct CfRun {
         DevBuf<unsigned long long> c1(1);
         HIP_OK(hipMemsetAsync(c1.p, 0, 8, st));
         if (w_hi > w_lo) launch_at(st, dim3(wgrid), dim3(kBlock), k_popcount, g->valid.p, w_lo, w_hi, c1.p);
-        out->stats[2] = read_counter(ctx, c1.p);
+        out->stats[2] = read_counter(st, c1.p);
         out->stats[3] = tips_after;
         if (n_cand) {
             DevBuf<uint8_t> fl(n_cand);
@@ -2491,12 +2467,8 @@ uint64_t graph_valid_out_ranks(const mcaat_graph *g, uint64_t *ids, uint32_t *nb
     if (!nw) return 0;
     DevBuf<uint64_t> pc(nw + 1), wpre(nw + 1);
     HIP_OK(hipMemsetAsync(pc.p + nw, 0, 8, st));
-    hipLaunchKernelGGL(k_word_popc, dim3(grid_for(nw, kBlock, (unsigned)g->ctx->n_cu * 16)), dim3(kBlock), 0, st,
-                       (const uint64_t *)g->valid.p, nw, pc.p);
-    LAUNCH_OK();
-    with_cub_temp([&](void *t, size_t &tmp) {
-        return hipcub::DeviceScan::ExclusiveSum(t, tmp, pc.p, wpre.p, (size_t)(nw + 1), st);
-    });
+    launch_at(st, dim3(grid_for(nw, kBlock, (unsigned)g->ctx->n_cu * 16)), dim3(kBlock), k_word_popc, g->valid.p, nw, pc.p);
+    excl_scan(st, pc.p, wpre.p, nw + 1);
     uint64_t n = 0;
     d2h(g->ctx, &n, wpre.p + nw, 8);
     if (!ids || !n) return n;
@@ -2504,9 +2476,8 @@ uint64_t graph_valid_out_ranks(const mcaat_graph *g, uint64_t *ids, uint32_t *nb
     DevBuf<uint64_t> di(n);
     DevBuf<uint32_t> dn(4 * n);
     DevBuf<uint8_t> dc(n);
-    hipLaunchKernelGGL(k_valid_out_ranks, dim3(grid_for(nw * 64, kBlock, (unsigned)g->ctx->n_cu * 32)), dim3(kBlock), 0,
-                       st, g->view(), (const uint64_t *)wpre.p, di.p, dn.p, dc.p);
-    LAUNCH_OK();
+    launch_at(st, dim3(grid_for(nw * 64, kBlock, (unsigned)g->ctx->n_cu * 32)), dim3(kBlock), k_valid_out_ranks, g->view(),
+              wpre.p, di.p, dn.p, dc.p);
     d2h(g->ctx, ids, di.p, 8 * n);
     d2h(g->ctx, nbr, dn.p, 16 * n);
     d2h(g->ctx, cnt, dc.p, n);
@@ -2520,9 +2491,7 @@ void graph_neighbors(const mcaat_graph *g, const uint64_t *ids, size_t n, int in
     DevBuf<uint64_t> di(n), dout(4 * n);
     DevBuf<int32_t> dc(n);
     HIP_OK(hipMemcpyAsync(di.p, ids, 8 * n, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_neighbors, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, st, g->view(), di.p, (uint64_t)n,
-                       incoming, dout.p, dc.p);
-    LAUNCH_OK();
+    launch_at(st, dim3(grid_for(n, kBlock)), dim3(kBlock), k_neighbors, g->view(), di.p, n, incoming, dout.p, dc.p);
     HIP_OK(hipMemcpyAsync(out, dout.p, 32 * n, hipMemcpyDeviceToHost, st));
     HIP_OK(hipMemcpyAsync(counts, dc.p, 4 * n, hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
@@ -2543,9 +2512,8 @@ void graph_gather(const mcaat_graph *g, const uint64_t *ids, size_t n, uint64_t 
     DevBuf<uint64_t> di(n), dk(keys ? n : 1);
     DevBuf<uint16_t> dm(mult ? n : 1);
     HIP_OK(hipMemcpyAsync(di.p, ids, 8 * n, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_gather_key_mult, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, st, g->key.p, g->mult.p, di.p,
-                       (uint64_t)n, keys ? dk.p : (uint64_t *)nullptr, mult ? dm.p : (uint16_t *)nullptr);
-    LAUNCH_OK();
+    launch_at(st, dim3(grid_for(n, kBlock)), dim3(kBlock), k_gather_key_mult, g->key.p, g->mult.p, di.p, n,
+              keys ? dk.p : nullptr, mult ? dm.p : nullptr);
     if (keys) HIP_OK(hipMemcpyAsync(keys, dk.p, 8 * n, hipMemcpyDeviceToHost, st));
     if (mult) HIP_OK(hipMemcpyAsync(mult, dm.p, 2 * n, hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
@@ -2559,9 +2527,7 @@ void graph_set_valid(mcaat_graph *g, const uint64_t *ids, size_t n, int valid) {
     DevBuf<uint64_t> di(n);
     HIP_OK(hipMemcpyAsync(di.p, ids, 8 * n, hipMemcpyHostToDevice, st));
     if (!valid) g->all_valid = false;
-    hipLaunchKernelGGL(k_set_bits, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, st, g->valid.p, di.p, (uint64_t)n,
-                       valid);
-    LAUNCH_OK();
+    launch_at(st, dim3(grid_for(n, kBlock)), dim3(kBlock), k_set_bits, g->valid.p, di.p, n, valid);
     HIP_OK(hipStreamSynchronize(st));
 }
 
@@ -2569,8 +2535,7 @@ void graph_download_valid(const mcaat_graph *g, uint8_t *valid) {
     if (!g->D) return;
     hipStream_t st = g->ctx->stream;
     DevBuf<uint8_t> d(g->D);
-    hipLaunchKernelGGL(k_unpack_bits, dim3(grid_for(g->D, kBlock)), dim3(kBlock), 0, st, g->valid.p, g->D, d.p);
-    LAUNCH_OK();
+    launch_at(st, dim3(grid_for(g->D, kBlock)), dim3(kBlock), k_unpack_bits, g->valid.p, g->D, d.p);
     HIP_OK(hipMemcpyAsync(valid, d.p, g->D, hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
 }

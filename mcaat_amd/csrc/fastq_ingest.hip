@@ -482,13 +482,10 @@ void ingest_fastq(mcaat_ctx *ctx, const char *const *files, int n_files, mcaat_r
                 HIP_OK(hipStreamWaitEvent(ctx->stream, up_ev[cur], 0));
                 KernelTimer kt(ctx, "fq_parse", 2.0 * (double)total);
                 HIP_OK(hipMemsetAsync(cnt.p + nseg, 0, 4, ctx->stream));
-                hipLaunchKernelGGL(k_fq_nlcount, dim3(grid_for(nseg, kBlock)), dim3(kBlock), 0, ctx->stream,
-                                   dbufs[cur].p, nseg, cnt.p);
-                LAUNCH_OK();
+                launch_at(ctx->stream, dim3(grid_for(nseg, kBlock)), dim3(kBlock), k_fq_nlcount, dbufs[cur].p, nseg, cnt.p);
                 scan_u32(ctx, cnt.p, first.p, (uint64_t)nseg + 1, tmp);
-                hipLaunchKernelGGL(k_fq_nlpos, dim3(grid_for(nseg, kBlock)), dim3(kBlock), 0, ctx->stream,
-                                   dbufs[cur].p, nseg, first.p, nl.p);
-                LAUNCH_OK();
+                launch_at(ctx->stream, dim3(grid_for(nseg, kBlock)), dim3(kBlock), k_fq_nlpos, dbufs[cur].p, nseg, first.p,
+                          nl.p);
                 HIP_OK(hipMemcpyAsync(hmeta, first.p + nseg, 4, hipMemcpyDeviceToHost, ctx->stream));
                 HIP_OK(hipStreamSynchronize(ctx->stream));
                 kt.stop();
@@ -532,9 +529,8 @@ void ingest_fastq(mcaat_ctx *ctx, const char *const *files, int n_files, mcaat_r
                 }
                 HIP_OK(hipMemsetAsync(meta.p, 0, 4, ctx->stream));
                 for (auto *b : {&nbase, &nrun, &slen}) HIP_OK(hipMemsetAsync(b->p + nrec, 0, 4, ctx->stream));
-                hipLaunchKernelGGL(k_fq_records, dim3(grid_for(nrec, kBlock)), dim3(kBlock), 0, ctx->stream, dbufs[cur].p,
-                                   nl.p, nrec, sbeg.p, slen.p, nbase.p, nrun.p, meta.p);
-                LAUNCH_OK();
+                launch_at(ctx->stream, dim3(grid_for(nrec, kBlock)), dim3(kBlock), k_fq_records, dbufs[cur].p, nl.p, nrec,
+                          sbeg.p, slen.p, nbase.p, nrun.p, meta.p);
                 scan_u32(ctx, nbase.p, boff.p, (uint64_t)nrec + 1, tmp);
                 scan_u32(ctx, nrun.p, roff.p, (uint64_t)nrec + 1, tmp);
                 scan_u32(ctx, slen.p, qoff.p, (uint64_t)nrec + 1, tmp);
@@ -553,10 +549,9 @@ void ingest_fastq(mcaat_ctx *ctx, const char *const *files, int n_files, mcaat_r
                 grow(ctx, qpacked, (q_bases + 31) / 32 + 1, (q_bases + cq + 31) / 32 + 17);
                 grow(ctx, qoffsets, n_rec + 1, n_rec + nrec + 2);
                 KernelTimer ke(ctx, "fq_emit", (double)consumed + 0.5 * (double)(cb + cq) + 8.0 * (cr + nrec));
-                hipLaunchKernelGGL(k_fq_emit, dim3(grid_for(nrec, kBlock)), dim3(kBlock), 0, ctx->stream, dbufs[cur].p, nrec,
-                                   sbeg.p, slen.p, boff.p, roff.p, qoff.p, n_bases, n_reads, q_bases, n_rec, fi > 0 ? 1 : 0,
-                                   packed.p, offsets.p, qpacked.p, qoffsets.p);
-                HIP_OK(hipGetLastError());
+                launch_at(ctx->stream, dim3(grid_for(nrec, kBlock)), dim3(kBlock), k_fq_emit, dbufs[cur].p, nrec, sbeg.p,
+                          slen.p, boff.p, roff.p, qoff.p, n_bases, n_reads, q_bases, n_rec, fi > 0 ? 1 : 0, packed.p,
+                          offsets.p, qpacked.p, qoffsets.p);
                 ke.stop();
                 n_bases += cb;
                 n_reads += cr;
@@ -582,8 +577,8 @@ void ingest_fastq(mcaat_ctx *ctx, const char *const *files, int n_files, mcaat_r
         uint64_t L = 0;
         HIP_OK(hipMemcpy(&L, offsets.p + 1, 8, hipMemcpyDeviceToHost));
         HIP_OK(hipMemsetAsync(meta.p, 0, 4, ctx->stream));
-        hipLaunchKernelGGL(k_fq_fixed_len, dim3(grid_for(n_reads + 1, kBlock)), dim3(kBlock), 0, ctx->stream,
-                           offsets.p, n_reads, L, meta.p);
+        launch_at(ctx->stream, dim3(grid_for(n_reads + 1, kBlock)), dim3(kBlock), k_fq_fixed_len, offsets.p, n_reads, L,
+                  meta.p);
         HIP_OK(hipMemcpyAsync(hmeta, meta.p, 4, hipMemcpyDeviceToHost, ctx->stream));
         HIP_OK(hipStreamSynchronize(ctx->stream));
         if (!hmeta[0] && L > 0) r->fixed_len = L;

@@ -573,7 +573,7 @@ bool fastq_hostpack(mcaat_ctx *ctx, const char *const *files, int n_files,
             } catch (const Error &x) {
                 (void)hipGetLastError();
                 ahead.reset();
-                if (getenv("MCAAT_VERBOSE") && getenv("MCAAT_VERBOSE")[0] == '1')
+                if (verbose())
                     fprintf(stderr, "[mcaat] fq: count ahead skipped (%s)\n", x.what());
             }
             verbose_mark(ctx, "fq.ahead_begin");
@@ -614,8 +614,7 @@ bool fastq_hostpack(mcaat_ctx *ctx, const char *const *files, int n_files,
         job(0);
         for (auto &th : pool) th.join();
     }
-    static const bool verbose = getenv("MCAAT_VERBOSE") && getenv("MCAAT_VERBOSE")[0] == '1';
-    if (verbose) {
+    if (verbose()) {
         const auto mm = std::minmax_element(busy.begin(), busy.end());
         fprintf(stderr, "[mcaat] fq: %d parts, %d workers, busy %.3f .. %.3f s\n", P, NW, *mm.first, *mm.second);
     }
@@ -650,16 +649,14 @@ bool fastq_hostpack(mcaat_ctx *ctx, const char *const *files, int n_files,
     HIP_OK(hipMemsetAsync(r->packed.p + n_words, 0, 8 * 64, st));
     if (n_words) {
         KernelTimer kt(ctx, "fq_concat", 16.0 * (double)n_words);
-        hipLaunchKernelGGL(k_concat_parts, dim3(grid_for(n_words, kPB, (unsigned)ctx->n_cu * 8)), dim3(kPB),
-                           P <= kConcatLdsParts ? (size_t)(2 * P + 1) * 8 : (size_t)0, st, regions.p, dregion.p, dstart.p, P, n_words, n_bases, r->packed.p);
-        LAUNCH_OK();
+        launch_lds(st, dim3(grid_for(n_words, kPB, (unsigned)ctx->n_cu * 8)), dim3(kPB),
+                   P <= kConcatLdsParts ? (size_t)(2 * P + 1) * 8 : (size_t)0, k_concat_parts, regions.p, dregion.p, dstart.p,
+                   P, n_words, n_bases, r->packed.p);
         kt.stop();
     }
     r->offsets.alloc(n_reads + 1);
     if (fixed) {
-        hipLaunchKernelGGL(k_offsets_fixed, dim3(grid_for(n_reads + 1, kPB)), dim3(kPB), 0, st, r->offsets.p, n_reads,
-                           (uint64_t)L);
-        LAUNCH_OK();
+        launch_at(st, dim3(grid_for(n_reads + 1, kPB)), dim3(kPB), k_offsets_fixed, r->offsets.p, n_reads, L);
     } else {
         std::vector<uint64_t> off(n_reads + 1, 0);
         uint64_t k = 0;
@@ -690,9 +687,8 @@ bool fastq_hostpack(mcaat_ctx *ctx, const char *const *files, int n_files,
         r->rec_packed.alloc(n_words + 64);
         HIP_OK(hipMemsetAsync(r->rec_packed.p + n_words, 0, 8 * 64, st));
         if (n_words) {
-            hipLaunchKernelGGL(k_mapping_view, dim3(grid_for(n_words, kPB)), dim3(kPB), 0, st, r->packed.p,
-                               r->offsets.p, n_reads, file_records[0], n_words, n_bases, r->rec_packed.p);
-            LAUNCH_OK();
+            launch_at(st, dim3(grid_for(n_words, kPB)), dim3(kPB), k_mapping_view, r->packed.p, r->offsets.p, n_reads,
+                      file_records[0], n_words, n_bases, r->rec_packed.p);
         }
         r->rec_offsets.alloc(n_reads + 1);
         HIP_OK(hipMemcpyAsync(r->rec_offsets.p, r->offsets.p, 8 * (n_reads + 1), hipMemcpyDeviceToDevice, st));

@@ -414,12 +414,32 @@ inline unsigned grid_for(uint64_t n, unsigned block, unsigned cap = 65535u * 16)
     return (unsigned)g;
 }
 
-// a kernel launch with the geometry given: the arguments converted to the kernel's parameter
-// types (a DevBuf's pointer to a pointer to const), the launch checked
+// a kernel launch with the geometry and the dynamic LDS bytes given: the arguments converted to
+// the kernel's parameter types (a DevBuf's pointer to a pointer to const), the launch checked
+template <class... P, class... A>
+void launch_lds(hipStream_t st, dim3 grid, dim3 block, size_t lds_bytes, void (*k)(P...), A &&...a) {
+    hipLaunchKernelGGL(k, grid, block, lds_bytes, st, static_cast<P>(a)...);
+    LAUNCH_OK();
+}
+// the same without dynamic LDS
 template <class... P, class... A>
 void launch_at(hipStream_t st, dim3 grid, dim3 block, void (*k)(P...), A &&...a) {
-    hipLaunchKernelGGL(k, grid, block, 0, st, static_cast<P>(a)...);
-    LAUNCH_OK();
+    launch_lds(st, grid, block, 0, k, std::forward<A>(a)...);
+}
+
+// a device counter's value on the host (a pageable copy); the stream is synchronised
+template <class T>
+T read_counter(hipStream_t st, const T *p) {
+    T h{};
+    HIP_OK(hipMemcpyAsync(&h, p, sizeof(T), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    return h;
+}
+
+// MCAAT_VERBOSE=1: diagnostics on stderr
+inline bool verbose() {
+    static const bool v = getenv("MCAAT_VERBOSE") && getenv("MCAAT_VERBOSE")[0] == '1';
+    return v;
 }
 
 // a hipcub device call: once for the size of its temporary storage, once with the storage

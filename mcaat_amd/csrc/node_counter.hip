@@ -35,7 +35,7 @@
 #include <type_traits>
 
 #include "desc_canon.h"
-#include "internal.h"
+#include "cub_helpers.h"
 
 namespace mcaat {
 
@@ -1700,14 +1700,6 @@ __global__ void k_sum_u32(const uint32_t *v, uint64_t n, unsigned long long *sum
     block_add(sum, acc);
 }
 
-template <class T>
-void exclusive_scan(mcaat_ctx *ctx, const T *in, T *out, uint64_t n) {
-    size_t tmp = 0;
-    HIP_OK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, in, out, (size_t)n, ctx->stream));
-    DevBuf<uint8_t> t(tmp);
-    HIP_OK(hipcub::DeviceScan::ExclusiveSum(t.p, tmp, in, out, (size_t)n, ctx->stream));
-}
-
 // L1 bucket capacities: the expected descriptors (density 2/(w+1) per edge + one per item) with
 // headroom, + one partially used and one prefetched reservation per (workgroup, bucket)
 std::vector<uint64_t> l1_caps(mcaat_ctx *ctx, const SkParams &P, uint64_t a_grid, uint64_t n_occ, uint64_t n_items,
@@ -1738,17 +1730,12 @@ uint64_t set_regions(NcBuckets &bk, const std::vector<uint64_t> &base, const std
     return n_desc;
 }
 
-bool verbose_on() {
-    static const bool on = getenv("MCAAT_VERBOSE") && getenv("MCAAT_VERBOSE")[0] == '1';
-    return on;
-}
-
 }  // namespace
 
 // MCAAT_VERBOSE=1: host wall-clock marks of the sub-stages on stderr (stream-synchronised)
 void verbose_mark(mcaat_ctx *ctx, const char *what) {
     static double last = 0;
-    if (!verbose_on()) return;
+    if (!verbose()) return;
     timespec ts;
     clock_gettime(CLOCK_MONOTONIC, &ts);
     const double pre = ts.tv_sec * 1e3 + ts.tv_nsec / 1e6;
@@ -1841,27 +1828,19 @@ void node_counter_a(mcaat_ctx *ctx, const mcaat_reads *r, int k, const std::func
     } else if (r->n_reads) {
         DevBuf<uint64_t> cnt(r->n_reads + 1), start(r->n_reads + 1);
         HIP_OK(hipMemsetAsync(cnt.p, 0, cnt.bytes(), st));
-        hipLaunchKernelGGL(k_items_count, dim3(grid_for(r->n_reads, kBlock)), dim3(kBlock), 0, st, r->offsets.p,
-                           r->n_reads, E, cnt.p);
-        LAUNCH_OK();
-        exclusive_scan(ctx, cnt.p, start.p, r->n_reads + 1);
-        HIP_OK(hipMemcpyAsync(&n_items, start.p + r->n_reads, 8, hipMemcpyDeviceToHost, st));
-        HIP_OK(hipStreamSynchronize(st));
+        launch_at(st, dim3(grid_for(r->n_reads, kBlock)), dim3(kBlock), k_items_count, r->offsets.p, r->n_reads, E, cnt.p);
+        excl_scan(st, (const uint64_t *)cnt.p, start.p, r->n_reads + 1);
+        n_items = read_counter(st, start.p + r->n_reads);
         item_base.alloc(n_items);
         item_np.alloc(n_items);
-        hipLaunchKernelGGL(k_items_fill, dim3(grid_for(r->n_reads, kBlock)), dim3(kBlock), 0, st, r->offsets.p,
-                           r->n_reads, E, start.p, item_base.p, item_np.p);
-        LAUNCH_OK();
+        launch_at(st, dim3(grid_for(r->n_reads, kBlock)), dim3(kBlock), k_items_fill, r->offsets.p, r->n_reads, E, start.p,
+                  item_base.p, item_np.p);
         {  // occurrences = sum of the items' positions (reduced on the device)
             DevBuf<unsigned long long> socc(1);
             HIP_OK(hipMemsetAsync(socc.p, 0, 8, st));
-            hipLaunchKernelGGL(k_sum_u32, dim3(grid_for(n_items, kBlock, (unsigned)ctx->n_cu * 8)), dim3(kBlock), 0, st,
-                               item_np.p, n_items, socc.p);
-            LAUNCH_OK();
-            unsigned long long h = 0;
-            HIP_OK(hipMemcpyAsync(&h, socc.p, 8, hipMemcpyDeviceToHost, st));
-            HIP_OK(hipStreamSynchronize(st));
-            n_occ = h;
+            launch_at(st, dim3(grid_for(n_items, kBlock, (unsigned)ctx->n_cu * 8)), dim3(kBlock), k_sum_u32, item_np.p,
+                      n_items, socc.p);
+            n_occ = read_counter(st, socc.p);
         }
         src.item_base = item_base.p;
         src.item_np = item_np.p;
@@ -1909,9 +1888,8 @@ void node_counter_a(mcaat_ctx *ctx, const mcaat_reads *r, int k, const std::func
         if (a_stats) HIP_OK(hipMemsetAsync(dslots.p, 0, dslots.bytes(), st));
         {
             KernelTimer kt(ctx, "sk_scatter", 0.0);  // bytes added below, once the descriptor count is known
-            hipLaunchKernelGGL(sk_kernel(P.w, P.m == 16), dim3((unsigned)a_grid), dim3(kAThreads), 0, st, r->packed.p, src, P, l1.p,
-                               dbase.p, dcap.p, dcur.p, l1s.p, prof_a ? dprof.p : nullptr, nullptr, 0, a_stats ? dslots.p : nullptr);
-            LAUNCH_OK();
+            launch_at(st, dim3((unsigned)a_grid), dim3(kAThreads), sk_kernel(P.w, P.m == 16), r->packed.p, src, P, l1.p, dbase.p,
+                      dcap.p, dcur.p, l1s.p, prof_a ? dprof.p : nullptr, nullptr, 0, a_stats ? dslots.p : nullptr);
             kt.stop();
         }
         HIP_OK(hipMemcpyAsync(tot.data(), dcur.p, 8 * 256, hipMemcpyDeviceToHost, st));
@@ -2011,10 +1989,8 @@ void nc_ahead_part(NcAhead &a, const uint64_t *packed, uint64_t n_reads, uint64_
     const uint64_t npos = L - E + 1;
     src.ipr = (npos + kItem - 1) / kItem;
     a.n_occ += n_reads * npos;
-    hipLaunchKernelGGL(sk_kernel(a.P.w, a.P.m == 16), dim3((unsigned)a.a_grid), dim3(kAThreads), 0, a.ctx->side, packed,
-                       src, a.P, a.bk->data.p, (const uint64_t *)a.dbase.p, (const uint64_t *)a.dcap.p, a.dcur.p,
-                       a.bk->sub.p, nullptr, a.state.p, a.launches ? 2 : 1, nullptr);
-    LAUNCH_OK();
+    launch_at(a.ctx->side, dim3((unsigned)a.a_grid), dim3(kAThreads), sk_kernel(a.P.w, a.P.m == 16), packed, src, a.P,
+              a.bk->data.p, a.dbase.p, a.dcap.p, a.dcur.p, a.bk->sub.p, nullptr, a.state.p, a.launches ? 2 : 1, nullptr);
     ++a.launches;
 }
 
@@ -2031,10 +2007,9 @@ std::shared_ptr<NcBuckets> nc_ahead_end(NcAhead &a) {
     std::vector<unsigned long long> tot(256, 0);
     if (!a.failed) {
         ItemSrc src{};
-        hipLaunchKernelGGL(sk_kernel(a.P.w, a.P.m == 16), dim3((unsigned)a.a_grid), dim3(kAThreads), 0, ctx->side,
-                           (const uint64_t *)a.bk->data.p, src, a.P, a.bk->data.p, (const uint64_t *)a.dbase.p,
-                           (const uint64_t *)a.dcap.p, a.dcur.p, a.bk->sub.p, nullptr, a.state.p, a.launches ? 3 : 0, nullptr);
-        LAUNCH_OK();
+        launch_at(ctx->side, dim3((unsigned)a.a_grid), dim3(kAThreads), sk_kernel(a.P.w, a.P.m == 16),
+                  (const uint64_t *)a.bk->data.p, src, a.P, a.bk->data.p, a.dbase.p, a.dcap.p, a.dcur.p, a.bk->sub.p, nullptr,
+                  a.state.p, a.launches ? 3 : 0, nullptr);
         HIP_OK(hipMemcpyAsync(tot.data(), a.dcur.p, 8 * 256, hipMemcpyDeviceToHost, ctx->side));
     }
     HIP_OK(hipStreamSynchronize(ctx->side));
@@ -2099,20 +2074,16 @@ void plan_b(mcaat_ctx *ctx, NcBuckets &bk, uint64_t n_desc, BPlan &pl) {
     druns.alloc(nch * S ? nch * S : 1);  // per chunk and sub: count, then run start (lines)
     {
         KernelTimer kt(ctx, "l2_hist", 2.0 * (double)n_desc);
-        if (nch) {
-            hipLaunchKernelGGL(k_l2_hist, dim3((unsigned)nch), dim3(kBThreads), 4 * S, st, bk.sub.p, dcs.p, dcl.p, dcb.p,
-                               l2_bits, dtot.p, druns.p);
-            LAUNCH_OK();
-        }
-        exclusive_scan(ctx, (const uint64_t *)dtot.p, dfine.p, F + 1);
+        if (nch)
+            launch_lds(st, dim3((unsigned)nch), dim3(kBThreads), 4 * S, k_l2_hist, bk.sub.p, dcs.p, dcl.p, dcb.p, l2_bits, dtot.p,
+                       druns.p);
+        excl_scan(st, (const uint64_t *)dtot.p, dfine.p, F + 1);
         d2h(ctx, hfine.data(), dfine.p, 8 * (F + 1));
         if (hfine[F] / kLG >= (1ull << 32)) throw Error(MCAAT_E_CAPACITY, "node_counter: 2^32 or more fine-partition lines");
         if (nch) {
             DevBuf<uint64_t> dbch(257);
             HIP_OK(hipMemcpyAsync(dbch.p, bchunk.data(), 8 * 257, hipMemcpyHostToDevice, st));
-            hipLaunchKernelGGL(k_chunk_runs, dim3(grid_for(256ull * S, 256)), dim3(256), 0, st, druns.p,
-                               (const uint64_t *)dbch.p, (const uint64_t *)dfine.p, S);
-            LAUNCH_OK();
+            launch_at(st, dim3(grid_for(256ull * S, 256)), dim3(256), k_chunk_runs, druns.p, dbch.p, dfine.p, S);
             HIP_OK(hipStreamSynchronize(st));  // dbch is freed on scope exit
         }
         kt.stop();
@@ -2211,9 +2182,8 @@ void node_counter_preagg(mcaat_ctx *ctx, NcBuckets &bk, int k, NcBuckets &out, u
     HIP_OK(hipMemsetAsync(dlive.p, 0, dlive.bytes(), st));
     HIP_OK(hipMemsetAsync(dcur.p, 0, dcur.bytes(), st));
     HIP_OK(hipMemsetAsync(dstat.p, 0, dstat.bytes(), st));
-    hipLaunchKernelGGL(k_live_count, dim3((unsigned)std::min<uint64_t>(plan.nch, (uint64_t)ctx->n_cu * 8)), dim3(kBlock), 0,
-                       st, bk.sub.p, plan.dcs.p, plan.dcl.p, plan.dcb.p, plan.nch, dlive.p);
-    LAUNCH_OK();
+    launch_at(st, dim3((unsigned)std::min<uint64_t>(plan.nch, (uint64_t)ctx->n_cu * 8)), dim3(kBlock), k_live_count,
+              bk.sub.p, plan.dcs.p, plan.dcl.p, plan.dcb.p, plan.nch, dlive.p);
     std::vector<unsigned long long> live(256), cur(256);
     d2h(ctx, live.data(), dlive.p, 8 * 256);
     std::vector<uint64_t> rbase(256), rcap(256);
@@ -2239,24 +2209,19 @@ void node_counter_preagg(mcaat_ctx *ctx, NcBuckets &bk, int k, NcBuckets &out, u
         g.fine.alloc(g.gn);
         {
             KernelTimer kt(ctx, "preagg_partition", 32.0 * (double)g.gn);
-            hipLaunchKernelGGL(k_l2_scatter<false>, dim3((unsigned)(g.c1 - g.c0)), dim3(kBThreads), 0, st, bk.data.p,
-                               plan.dcs.p + g.c0, plan.dcl.p + g.c0, (const uint32_t *)plan.druns.p + g.c0 * S, bk.l2_bits, E,
-                               g.fine.p, g.gbase, (const uint32_t *)nullptr, (uint32_t *)nullptr);
-            LAUNCH_OK();
+            launch_at(st, dim3((unsigned)(g.c1 - g.c0)), dim3(kBThreads), k_l2_scatter<false>, bk.data.p, plan.dcs.p + g.c0,
+                      plan.dcl.p + g.c0, plan.druns.p + g.c0 * S, bk.l2_bits, E, g.fine.p, g.gbase, nullptr, nullptr);
             kt.stop();
         }
         KernelTimer kt(ctx, "desc_preagg", 16.0 * (double)g.gn);
         const unsigned wg = (unsigned)std::min<uint64_t>(g.p1 - g.p0, (uint64_t)kCPerCu * ctx->n_cu);
-        hipLaunchKernelGGL(k_desc_preagg, dim3(wg), dim3(kPThreads), 0, st, g.fine.p, g.gbase, plan.dfine.p, g.p0, g.p1,
-                           bk.l2_bits, out.data.p, out.sub.p, out.wgt.p, (const uint64_t *)drb.p,
-                           (const uint64_t *)drc.p, dcur.p, lim.dmax[0], lim.split_first[0], lim.split_max, dstat.p);
-        LAUNCH_OK();
+        launch_at(st, dim3(wg), dim3(kPThreads), k_desc_preagg, g.fine.p, g.gbase, plan.dfine.p, g.p0, g.p1, bk.l2_bits,
+                  out.data.p, out.sub.p, out.wgt.p, drb.p, drc.p, dcur.p, lim.dmax[0], lim.split_first[0], lim.split_max,
+                  dstat.p);
         kt.stop();  // waits for the launch: the group's buffer goes back after it
         g.fine.release();
     }
-    hipLaunchKernelGGL(k_preagg_pad, dim3(1), dim3(256), 0, st, out.data.p, out.sub.p, out.wgt.p, (const uint64_t *)drb.p,
-                       (const uint64_t *)drc.p, (const unsigned long long *)dcur.p);
-    LAUNCH_OK();
+    launch_at(st, dim3(1), dim3(256), k_preagg_pad, out.data.p, out.sub.p, out.wgt.p, drb.p, drc.p, dcur.p);
     unsigned long long hs[2];
     d2h(ctx, cur.data(), dcur.p, 8 * 256);
     d2h(ctx, hs, dstat.p, 16);
@@ -2350,13 +2315,10 @@ void node_counter_bc(mcaat_ctx *ctx, NcBuckets &bk, int k, CountResult &out) {
         }
         // descriptors read, descriptors written
         btimers.push_back(std::make_unique<KernelTimer>(ctx, "l2_partition", 32.0 * (double)g.gn, sb));
-        if (g.c1 > g.c0) {
-            hipLaunchKernelGGL(weighted ? k_l2_scatter<true> : k_l2_scatter<false>, dim3((unsigned)(g.c1 - g.c0)),
-                               dim3(kBThreads), 0, sb, bk.data.p, plan.dcs.p + g.c0, plan.dcl.p + g.c0,
-                               (const uint32_t *)plan.druns.p + g.c0 * S, bk.l2_bits, E, g.fine.p, g.gbase,
-                               (const uint32_t *)bk.wgt.p, g.finew.p);
-            LAUNCH_OK();
-        }
+        if (g.c1 > g.c0)
+            launch_at(sb, dim3((unsigned)(g.c1 - g.c0)), dim3(kBThreads), weighted ? k_l2_scatter<true> : k_l2_scatter<false>,
+                      bk.data.p, plan.dcs.p + g.c0, plan.dcl.p + g.c0, plan.druns.p + g.c0 * S, bk.l2_bits, E, g.fine.p,
+                      g.gbase, bk.wgt.p, g.finew.p);
         btimers.back()->mark();
         g.done = event_get(ctx);
         HIP_OK(hipEventRecord(g.done, sb));
@@ -2373,11 +2335,9 @@ void node_counter_bc(mcaat_ctx *ctx, NcBuckets &bk, int k, CountResult &out) {
     auto launch_c = [&](int tier, const BGroup &g) {
         KernelTimer kt(ctx, "lds_count", 16.0 * (double)g.gn);
         const unsigned wg = (unsigned)std::min<uint64_t>(g.p1 - g.p0, (uint64_t)(tier == 2 ? 1 : kCPerCu) * ctx->n_cu);
-        hipLaunchKernelGGL(c_kernels[weighted][2 - tier][!prof_c], dim3(wg), dim3(kCThreads), 0, st, g.fine.p, g.gbase,
-                           plan.dfine.p, g.p0, g.p1, E, out.keys.p, out.counts.p, out_cap, dcnt.p, ovf_list.p, dcnt.p + 1,
-                           lim.cap_max[tier], lim.dmax[tier], dcnt.p + 2, lim.split_first[tier], lim.split_max,
-                           prof_c ? dprof.p : nullptr, (const uint32_t *)g.finew.p);
-        LAUNCH_OK();
+        launch_at(st, dim3(wg), dim3(kCThreads), c_kernels[weighted][2 - tier][!prof_c], g.fine.p, g.gbase, plan.dfine.p, g.p0,
+                  g.p1, E, out.keys.p, out.counts.p, out_cap, dcnt.p, ovf_list.p, dcnt.p + 1, lim.cap_max[tier], lim.dmax[tier],
+                  dcnt.p + 2, lim.split_first[tier], lim.split_max, prof_c ? dprof.p : nullptr, g.finew.p);
         kt.stop();
     };
     // global-table fallback for the n_ovf (partition, class) entries of ovf_list whose distinct edges
@@ -2385,9 +2345,8 @@ void node_counter_bc(mcaat_ctx *ctx, NcBuckets &bk, int k, CountResult &out) {
     auto count_overflowed = [&](const BGroup &g, uint64_t n_ovf) -> uint64_t {
         const uint32_t *wgt = g.finew.p;  // set: (descriptor, multiplicity) records
         DevBuf<uint64_t> occ(n_ovf);
-        hipLaunchKernelGGL(wgt ? k_part_occ<true> : k_part_occ<false>, dim3((unsigned)std::min<uint64_t>(n_ovf, 65536)),
-                           dim3(kBlock), 0, st, g.fine.p, g.gbase, plan.dfine.p, ovf_list.p, n_ovf, occ.p, wgt);
-        LAUNCH_OK();
+        launch_at(st, dim3((unsigned)std::min<uint64_t>(n_ovf, 65536)), dim3(kBlock), wgt ? k_part_occ<true> : k_part_occ<false>,
+                  g.fine.p, g.gbase, plan.dfine.p, ovf_list.p, n_ovf, occ.p, wgt);
         std::vector<uint64_t> occ_h(n_ovf);
         std::vector<uint32_t> parts_h(n_ovf);
         d2h(ctx, occ_h.data(), occ.p, 8 * n_ovf);
@@ -2407,29 +2366,21 @@ void node_counter_bc(mcaat_ctx *ctx, NcBuckets &bk, int k, CountResult &out) {
                 HIP_OK(hipMemsetAsync(tab.p, 0, tab.bytes(), st));
                 HIP_OK(hipMemsetAsync(nn.p, 0, 8, st));
                 HIP_OK(hipMemsetAsync(dover.p, 0, 4, st));
-                hipLaunchKernelGGL(wgt ? k_fallback<true> : k_fallback<false>,
-                                   dim3((unsigned)std::min<uint64_t>(q1 - q0, 65536)), dim3(kBlock), 0, st, g.fine.p, g.gbase,
-                                   plan.dfine.p, dparts.p, q1 - q0, E, tab.p, tcap - 1, nn.p, dover.p, wgt);
-                LAUNCH_OK();
-                int over = 0;
-                HIP_OK(hipMemcpyAsync(&over, dover.p, 4, hipMemcpyDeviceToHost, st));
-                HIP_OK(hipStreamSynchronize(st));
-                if (over) {
+                launch_at(st, dim3((unsigned)std::min<uint64_t>(q1 - q0, 65536)), dim3(kBlock),
+                          wgt ? k_fallback<true> : k_fallback<false>, g.fine.p, g.gbase, plan.dfine.p, dparts.p, q1 - q0, E, tab.p,
+                          tcap - 1, nn.p, dover.p, wgt);
+                if (read_counter(st, dover.p)) {
                     tcap <<= 1;
                     continue;
                 }
-                hipLaunchKernelGGL(k_fallback_emit, dim3(grid_for(tcap, kBlock, 65536)), dim3(kBlock), 0, st, tab.p, tcap,
-                                   out.keys.p, out.counts.p, out_cap, dcnt.p);
-                LAUNCH_OK();
+                launch_at(st, dim3(grid_for(tcap, kBlock, 65536)), dim3(kBlock), k_fallback_emit, tab.p, tcap, out.keys.p,
+                          out.counts.p, out_cap, dcnt.p);
                 HIP_OK(hipStreamSynchronize(st));
                 break;
             }
             q0 = q1;
         }
-        unsigned long long total = 0;
-        HIP_OK(hipMemcpyAsync(&total, dcnt.p, 8, hipMemcpyDeviceToHost, st));
-        HIP_OK(hipStreamSynchronize(st));
-        return total;
+        return read_counter(st, dcnt.p);
     };
     uint64_t n_out = 0;
     if (!groups.empty()) launch_b(groups[0]);
@@ -2458,7 +2409,7 @@ void node_counter_bc(mcaat_ctx *ctx, NcBuckets &bk, int k, CountResult &out) {
                 break;
             }
             if (attempt > 0) throw Error(MCAAT_E_CAPACITY, "node_counter: output sizing failed");
-            if (verbose_on())
+            if (verbose())
                 fprintf(stderr, "[mcaat] node_counter: group %zu overflowed the output (%llu > %llu): re-count\n", gi,
                         (unsigned long long)total, (unsigned long long)out_cap);
             // grow (keeping the groups already counted) and count this group again
@@ -2482,7 +2433,7 @@ void node_counter_bc(mcaat_ctx *ctx, NcBuckets &bk, int k, CountResult &out) {
             const double need = (double)n_out / frac;
             const uint64_t est = (uint64_t)(need * 1.08) + (1u << 20);
             if (need > (double)out_cap) {
-                if (verbose_on())
+                if (verbose())
                     fprintf(stderr, "[mcaat] node_counter: output grown after group %zu (%llu distinct, %.4f of the descriptors): %llu -> %llu\n",
                             gi, (unsigned long long)n_out, frac, (unsigned long long)out_cap, (unsigned long long)est);
                 // the next group's pass B (side stream) may be handed the old buffers: the arena
@@ -2518,15 +2469,9 @@ void node_counter_bc(mcaat_ctx *ctx, NcBuckets &bk, int k, CountResult &out) {
 
 void sort_counts(mcaat_ctx *ctx, CountResult &c, int k) {
     if (c.n < 2) return;
-    const int E = k + 1;
     DevBuf<uint64_t> k2(c.n);
     DevBuf<uint32_t> c2(c.n);
-    size_t tmp = 0;
-    HIP_OK(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp, c.keys.p, k2.p, c.counts.p, c2.p, (size_t)c.n, 0, 2 * E,
-                                              ctx->stream));
-    DevBuf<uint8_t> t(tmp);
-    HIP_OK(hipcub::DeviceRadixSort::SortPairs(t.p, tmp, c.keys.p, k2.p, c.counts.p, c2.p, (size_t)c.n, 0, 2 * E,
-                                              ctx->stream));
+    sort_pairs(ctx->stream, c.keys.p, k2.p, c.counts.p, c2.p, c.n, 2 * (k + 1));
     HIP_OK(hipStreamSynchronize(ctx->stream));
     c.keys = std::move(k2);
     c.counts = std::move(c2);

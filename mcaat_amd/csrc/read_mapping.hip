@@ -24,7 +24,7 @@
 
 #include <algorithm>
 
-#include "internal.h"
+#include "cub_helpers.h"
 
 namespace mcaat {
 namespace {
@@ -112,14 +112,6 @@ __global__ void __launch_bounds__(kBlock) k_and_bits(uint64_t *valid, const uint
     for (uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; w < nw; w += stride) valid[w] &= keep[w];
 }
 
-template <class F>
-void cub_call(hipStream_t st, F &&f) {
-    size_t tmp = 0;
-    HIP_OK(f(nullptr, tmp));
-    DevBuf<uint8_t> t(tmp ? tmp : 1);
-    HIP_OK(f(t.p, tmp));
-}
-
 }  // namespace
 
 void map_reads(const mcaat_graph *g, const mcaat_reads *r, const uint64_t *nodes, size_t n_nodes,
@@ -142,27 +134,23 @@ void map_reads(const mcaat_graph *g, const mcaat_reads *r, const uint64_t *nodes
     DevBuf<uint64_t> slot(cap), dn(n_nodes);
     HIP_OK(hipMemsetAsync(slot.p, 0xFF, 8 * cap, st));
     HIP_OK(hipMemcpyAsync(dn.p, nodes, 8 * n_nodes, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_label_set, dim3(grid_for(n_nodes, kBlock)), dim3(kBlock), 0, st, g->key.p, g->D, dn.p,
-                       (uint64_t)n_nodes, (unsigned long long *)slot.p, cap - 1);
-    LAUNCH_OK();
+    launch_at(st, dim3(grid_for(n_nodes, kBlock)), dim3(kBlock), k_label_set, g->key.p, g->D, dn.p, n_nodes,
+              (unsigned long long *)slot.p, cap - 1);
 
     // 2. end probes
     DevBuf<uint64_t> nid(n_rec);
     DevBuf<uint8_t> hit(n_rec);
-    hipLaunchKernelGGL(k_map_ends, dim3(grid_for(n_rec, kBlock, 8 * ctx->n_cu * 8)), dim3(kBlock), 0, st, packed, off,
-                       n_rec, K, slot.p, cap - 1, nid.p, hit.p);
-    LAUNCH_OK();
+    launch_at(st, dim3(grid_for(n_rec, kBlock, 8 * ctx->n_cu * 8)), dim3(kBlock), k_map_ends, packed, off, n_rec, K, slot.p,
+              cap - 1, nid.p, hit.p);
     timer.mark("map_ends");
 
     // 3. hit records in order, their id offsets
     DevBuf<uint64_t> hrec(n_rec), dcount(1);
     hipcub::CountingInputIterator<uint64_t> it(0);
-    cub_call(st, [&](void *t, size_t &b) {
+    with_cub_temp([&](void *t, size_t &b) {
         return hipcub::DeviceSelect::Flagged(t, b, it, hit.p, hrec.p, dcount.p, (size_t)n_rec, st);
     });
-    uint64_t n_hit = 0;
-    HIP_OK(hipMemcpyAsync(&n_hit, dcount.p, 8, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
+    const uint64_t n_hit = read_counter(st, dcount.p);
     if (n_hit == 0) {
         timer.mark("map_ids");
         HIP_OK(hipStreamSynchronize(st));
@@ -172,10 +160,10 @@ void map_reads(const mcaat_graph *g, const mcaat_reads *r, const uint64_t *nodes
     DevBuf<uint64_t> hlen(n_hit), hpos(n_hit + 1);
     {
         // gather the hit lengths (select again on the counts, same flags => same order)
-        cub_call(st, [&](void *t, size_t &b) {
+        with_cub_temp([&](void *t, size_t &b) {
             return hipcub::DeviceSelect::Flagged(t, b, nid.p, hit.p, hlen.p, dcount.p, (size_t)n_rec, st);
         });
-        cub_call(st, [&](void *t, size_t &b) {
+        with_cub_temp([&](void *t, size_t &b) {
             return hipcub::DeviceScan::InclusiveSum(t, b, hlen.p, hpos.p + 1, (size_t)n_hit, st);
         });
         HIP_OK(hipMemsetAsync(hpos.p, 0, 8, st));
@@ -198,10 +186,8 @@ void map_reads(const mcaat_graph *g, const mcaat_reads *r, const uint64_t *nodes
         uint64_t h1 = h0 + 1;  // at least one record per batch
         while (h1 < n_hit && pos[h1 + 1] - pos[h0] <= bufn) ++h1;
         const uint64_t waves = h1 - h0;
-        hipLaunchKernelGGL(k_map_ids, dim3(grid_for(waves, kBlock / 64, 16 * ctx->n_cu * 4)), dim3(kBlock), 0, st,
-                           packed, off, K, g->key.p, g->D, g->dir.p, g->dir_shift, nprefix, hrec.p, hpos.p, h0, h1,
-                           ids.p);
-        LAUNCH_OK();
+        launch_at(st, dim3(grid_for(waves, kBlock / 64, 16 * ctx->n_cu * 4)), dim3(kBlock), k_map_ids, packed, off, K,
+                  g->key.p, g->D, g->dir.p, g->dir_shift, nprefix, hrec.p, hpos.p, h0, h1, ids.p);
         HIP_OK(hipMemcpyAsync(out->ids.data() + pos[h0], ids.p, 8 * (pos[h1] - pos[h0]), hipMemcpyDeviceToHost, st));
         HIP_OK(hipStreamSynchronize(st));
         h0 = h1;
@@ -258,9 +244,7 @@ void graph_keep_region(mcaat_graph *g, const uint64_t *seeds, size_t n, uint64_t
     if (n) {
         DevBuf<uint64_t> di(n);
         HIP_OK(hipMemcpyAsync(di.p, seeds, 8 * n, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_grow_seed, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, st, reg.p, di.p, (uint64_t)n, g->D,
-                           front.p, cnt.p);
-        LAUNCH_OK();
+        launch_at(st, dim3(grid_for(n, kBlock)), dim3(kBlock), k_grow_seed, reg.p, di.p, n, g->D, front.p, cnt.p);
         unsigned long long hn = 0;
         d2h(g->ctx, &hn, cnt.p, 8);
         nf = hn;
@@ -269,17 +253,14 @@ void graph_keep_region(mcaat_graph *g, const uint64_t *seeds, size_t n, uint64_t
         // membership is a bitmap, so each edge enters a frontier at most once: at most D entries
         DevBuf<uint64_t> next(std::min<uint64_t>(8 * nf, g->D));
         HIP_OK(hipMemsetAsync(cnt.p, 0, 8, st));
-        hipLaunchKernelGGL(k_grow_hop, dim3(grid_for(nf, kBlock)), dim3(kBlock), 0, st, g->view(), reg.p,
-                           (const uint64_t *)front.p, nf, next.p, cnt.p);
-        LAUNCH_OK();
+        launch_at(st, dim3(grid_for(nf, kBlock)), dim3(kBlock), k_grow_hop, g->view(), reg.p, front.p, nf, next.p, cnt.p);
         unsigned long long hn = 0;
         d2h(g->ctx, &hn, cnt.p, 8);
         nf = hn;
         front = std::move(next);
     }
-    hipLaunchKernelGGL(k_and_bits, dim3(grid_for(nw, kBlock)), dim3(kBlock), 0, st, g->valid.p, reg.p, nw);
+    launch_at(st, dim3(grid_for(nw, kBlock)), dim3(kBlock), k_and_bits, g->valid.p, reg.p, nw);
     g->all_valid = false;
-    LAUNCH_OK();
     HIP_OK(hipStreamSynchronize(st));
 }
 
@@ -292,14 +273,11 @@ void graph_keep_only(mcaat_graph *g, const uint64_t *ids, size_t n) {
     if (n) {
         DevBuf<uint64_t> di(n);
         HIP_OK(hipMemcpyAsync(di.p, ids, 8 * n, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_keep_bits, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, st, keep.p, di.p, (uint64_t)n,
-                           g->D);
-        LAUNCH_OK();
+        launch_at(st, dim3(grid_for(n, kBlock)), dim3(kBlock), k_keep_bits, keep.p, di.p, n, g->D);
         HIP_OK(hipStreamSynchronize(st));
     }
-    hipLaunchKernelGGL(k_and_bits, dim3(grid_for(nw, kBlock)), dim3(kBlock), 0, st, g->valid.p, keep.p, nw);
+    launch_at(st, dim3(grid_for(nw, kBlock)), dim3(kBlock), k_and_bits, g->valid.p, keep.p, nw);
     g->all_valid = false;
-    LAUNCH_OK();
     HIP_OK(hipStreamSynchronize(st));
 }
 

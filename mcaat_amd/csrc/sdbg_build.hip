@@ -11,7 +11,7 @@
 // position mask) -> valid bitmap.
 #include <hipcub/hipcub.hpp>
 
-#include "internal.h"
+#include "cub_helpers.h"
 
 namespace mcaat {
 
@@ -786,8 +786,8 @@ __global__ void __launch_bounds__(kL3Waves * 64) __attribute__((amdgpu_waves_per
 // sort does not drain them; round 2 loaded each 256-item round after the last had landed), and
 // the items go from those registers straight to their bins (padding skipped, no compaction
 // buffer): 24 KB of LDS, four workgroups per CU (the registers).
-template <int THREADS, int CAP, int OCC>
-__global__ void __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(OCC))) k_msd3_count(const uint64_t *in, const uint64_t *off2, const uint64_t *real2,
+template <int THREADS, int CAP>
+__global__ void __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4))) k_msd3_count(const uint64_t *in, const uint64_t *off2, const uint64_t *real2,
                                                         const uint64_t *base3, int k, const uint32_t *big, uint64_t nbig,
                                                         uint64_t *key, uint16_t *mult, uint32_t *fwd,
                                                         unsigned long long *nfwd, uint32_t limit) {
@@ -959,22 +959,6 @@ __global__ void __launch_bounds__(THREADS) k_msd3_block(const uint64_t *in, cons
     }
 }
 
-template <class T>
-void excl_scan(hipStream_t st, const T *in, T *out, uint64_t n) {
-    with_cub_temp([&](void *t, size_t &tmp) {
-        return hipcub::DeviceScan::ExclusiveSum(t, tmp, in, out, (size_t)n, st);
-    });
-}
-
-// a device counter's value on the host; the stream is synchronised
-template <class T>
-T read_counter(hipStream_t st, const T *p) {
-    T h{};
-    HIP_OK(hipMemcpyAsync(&h, p, sizeof(T), hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    return h;
-}
-
 constexpr uint64_t NB = (uint64_t)kMS * kMS;  // level-3 buckets
 
 // The n canonical (key, count) entries, which expand to D oriented edges, sorted into key / mult,
@@ -1112,18 +1096,17 @@ bool msd_sort(mcaat_ctx *ctx, const uint64_t *ckeys, const uint32_t *ccnt, uint6
                 DevBuf<uint32_t> big1(hb);
                 DevBuf<unsigned long long> nbig1(1);
                 HIP_OK(hipMemsetAsync(nbig1.p, 0, 8, st));
-                launch_at(st, grid(hb, 8), dim3(128), k_msd3_count<128, kSmallMid, 4>, l2.p, off2.p, real, base, k, big.p,
+                launch_at(st, grid(hb, 8), dim3(128), k_msd3_count<128, kSmallMid>, l2.p, off2.p, real, base, k, big.p,
                           hb, key, mult, big1.p, nbig1.p, limit("sort.small_limit", kSmallMid));
                 hb = read_counter(st, nbig1.p);
                 HIP_OK(hipMemcpyAsync(big.p, big1.p, 4 * hb, hipMemcpyDeviceToDevice, st));
             }
             // mid (deep graphs: D / 2^22 above the wave limit): 256-thread workgroups, 24 KB of LDS, four
-            // per CU by the registers (`sort.mid_occ=5`: five, at 96 registers with spills; C2 2 ms slower)
-            const int occ = knob(ctx, "sort.mid_occ", 4) >= 5 ? 5 : 4;
-            auto mid = occ == 5 ? k_msd3_count<256, kMidSort, 5> : k_msd3_count<256, kMidSort, 4>;
+            // per CU by the registers (five, at 96 registers with spills: C2 2 ms slower, C5 sdbg_build
+            // 149.7 -> 155.6 ms; profiles/r06_c5_knobs_ab.txt)
             if (hb)  // the small stage may have taken every listed bucket
-                launch_at(st, grid(hb, occ), dim3(256), mid, l2.p, off2.p, real, base, k, big.p, hb, key, mult, big2.p,
-                          nbig2.p, mid_limit);
+                launch_at(st, grid(hb, 4), dim3(256), k_msd3_count<256, kMidSort>, l2.p, off2.p, real, base, k, big.p, hb,
+                          key, mult, big2.p, nbig2.p, mid_limit);
             // block: the rare larger ones by one 1024-thread workgroup each
             const uint64_t hb2 = read_counter(st, nbig2.p);
             if (hb2)
@@ -1175,9 +1158,7 @@ void sdbg_build(mcaat_ctx *ctx, CountResult &c, int k, mcaat_graph *g) {
                   npal.p);
         DevBuf<uint64_t> sk(n2);
         DevBuf<uint16_t> sm(n2);
-        with_cub_temp([&](void *t, size_t &tmp) {
-            return hipcub::DeviceRadixSort::SortPairs(t, tmp, ek.p, sk.p, em.p, sm.p, (size_t)n2, 0, 2 * E + 1, st);
-        });
+        sort_pairs(st, ek.p, sk.p, em.p, sm.p, n2, 2 * E + 1);
         // palindromes left sentinels (1 << 2E) at the end
         if (D) {
             HIP_OK(hipMemcpyAsync(g->key.p, sk.p, 8 * D, hipMemcpyDeviceToDevice, st));

@@ -27,7 +27,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "internal.h"
+#include "cub_helpers.h"
 
 namespace mcaat {
 
@@ -527,47 +527,45 @@ struct SvBufs {
     }
 };
 
-template <class T>
-void ex_scan(mcaat_ctx *ctx, const T *in, uint64_t *out, uint64_t n) {
-    size_t tmp = 0;
-    HIP_OK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, in, out, (size_t)n, ctx->stream));
-    DevBuf<uint8_t> t(tmp ? tmp : 1);
-    HIP_OK(hipcub::DeviceScan::ExclusiveSum(t.p, tmp, in, out, (size_t)n, ctx->stream));
-}
-
+// The view's arrays, block by block: symbols -> edge-space rank structure and its samples ->
+// Estart -> sinks (sorted by W, id) -> node-space bitmaps -> node-space rank structure and its
+// samples -> hinstart. A block's scratch buffers go back to the arena where the block ends.
 SvView build_view(mcaat_graph *g, SvBufs &B, uint64_t *n_sinks) {
     mcaat_ctx *ctx = g->ctx;
     hipStream_t st = ctx->stream;
     const uint64_t D = g->D;
     const int k = g->k;
     auto grid = [&](uint64_t n) { return dim3(grid_for(n, kB, (unsigned)ctx->n_cu * 16)); };
+    // the last entry of an exclusive scan plus the last value scanned: the total
+    auto scan_total = [&](const uint64_t *abs, const uint32_t *raw, uint64_t n) {
+        uint64_t a = 0;
+        uint32_t r = 0;
+        d2h(ctx, &a, abs + n - 1, 8);
+        d2h(ctx, &r, raw + n - 1, 4);
+        return a + r;
+    };
     SvView v;
     v.D = D;
     v.valid = g->valid.p;
+
+    // symbols: one nibble per edge
     const uint64_t nsw = (D + 15) / 16, nb = (D + 63) / 64;
     B.sym.alloc(4 * nb + 1);  // whole blocks (the scans read 4 words per block)
     HIP_OK(hipMemsetAsync(B.sym.p, 0x88, B.sym.bytes(), st));  // nibbles past D match no kind
-    hipLaunchKernelGGL(k_sv_sym, grid(nsw), dim3(kB), 0, st, (const uint64_t *)g->key.p, D, B.sym.p);
-    LAUNCH_OK();
+    launch_at(st, grid(nsw), dim3(kB), k_sv_sym, g->key.p, D, B.sym.p);
     v.sym = B.sym.p;
-    // edge-space rank structure
+
+    // edge-space rank structure: per-block counts of the five kinds, scanned and packed; samples
     B.eblk.alloc(5 * nb);
     B.esb.alloc(5 * ((nb + 1023) / 1024));
     {
         DevBuf<uint32_t> raw(5 * nb);
         DevBuf<uint64_t> abs(5 * nb);
-        hipLaunchKernelGGL(k_sv_eblk_raw, grid(nb), dim3(kB), 0, st, (const uint64_t *)B.sym.p, nb, nsw, raw.p);
-        LAUNCH_OK();
-        for (int kd = 0; kd < 5; ++kd) ex_scan(ctx, raw.p + (uint64_t)kd * nb, abs.p + (uint64_t)kd * nb, nb);
-        hipLaunchKernelGGL(k_sv_pack, grid(nb), dim3(kB), 0, st, (const uint64_t *)abs.p, nb, 5, B.eblk.p, B.esb.p);
-        LAUNCH_OK();
-        for (int kd = 0; kd < 5; ++kd) {
-            uint64_t a = 0;
-            uint32_t r = 0;
-            d2h(ctx, &a, abs.p + (uint64_t)kd * nb + nb - 1, 8);
-            d2h(ctx, &r, raw.p + (uint64_t)kd * nb + nb - 1, 4);
-            v.ecount[kd] = a + r;
-        }
+        launch_at(st, grid(nb), dim3(kB), k_sv_eblk_raw, B.sym.p, nb, nsw, raw.p);
+        for (int kd = 0; kd < 5; ++kd)
+            excl_scan(st, (const uint32_t *)raw.p + (uint64_t)kd * nb, abs.p + (uint64_t)kd * nb, nb);
+        launch_at(st, grid(nb), dim3(kB), k_sv_pack, abs.p, nb, 5, B.eblk.p, B.esb.p);
+        for (int kd = 0; kd < 5; ++kd) v.ecount[kd] = scan_total(abs.p + (uint64_t)kd * nb, raw.p + (uint64_t)kd * nb, nb);
     }
     v.eblk = B.eblk.p;
     v.esb = B.esb.p;
@@ -575,40 +573,35 @@ SvView build_view(mcaat_graph *g, SvBufs &B, uint64_t *n_sinks) {
         B.es[kd].alloc((v.ecount[kd] >> kSamp) + 1);
         v.es[kd] = B.es[kd].p;
     }
-    hipLaunchKernelGGL(k_sv_esamples, grid(nb), dim3(kB), 0, st, v, nb, B.es[0].p, B.es[1].p, B.es[2].p, B.es[3].p, B.es[4].p);
-    LAUNCH_OK();
+    launch_at(st, grid(nb), dim3(kB), k_sv_esamples, v, nb, B.es[0].p, B.es[1].p, B.es[2].p, B.es[3].p, B.es[4].p);
     v.nodes = v.ecount[4];
-    // Estart[c]: the first edge whose label ends with c
-    {
-        std::vector<uint64_t> q(5);
-        for (int c = 0; c <= 4; ++c) q[c] = (uint64_t)c << (2 * k);  // BOSS key of the first label ending with c
-        for (int c = 0; c < 5; ++c) {
-            // lower bound on the host through a small device search (five values)
-            uint64_t lo = 0, hi = D;
-            while (lo < hi) {
-                const uint64_t mid = (lo + hi) / 2;
-                uint64_t km = 0;
-                d2h(ctx, &km, g->key.p + mid, 8);
-                if (km < q[c]) lo = mid + 1;
-                else hi = mid;
-            }
-            v.Estart[c] = lo;
+
+    // Estart[c]: the first edge whose label ends with c (BOSS key c << 2k), a lower bound on the
+    // host through single-key reads (five values)
+    for (int c = 0; c < 5; ++c) {
+        const uint64_t q = (uint64_t)c << (2 * k);
+        uint64_t lo = 0, hi = D;
+        while (lo < hi) {
+            const uint64_t mid = (lo + hi) / 2;
+            uint64_t km = 0;
+            d2h(ctx, &km, g->key.p + mid, 8);
+            if (km < q) lo = mid + 1;
+            else hi = mid;
         }
+        v.Estart[c] = lo;
     }
-    // sinks, sorted by (W, id)
+
+    // sinks, sorted by (W, id): the sinks per W first, then each W's flagged ids (a counting
+    // iterator: no id array)
     DevBuf<uint64_t> sink_edge;
     uint64_t ns = 0;
     std::vector<uint64_t> ns_c(4, 0);
     {
         DevBuf<uint8_t> flag(D ? D : 1);
-        hipLaunchKernelGGL(k_sv_sink_flags, grid(D), dim3(kB), 0, st, (const uint64_t *)B.sym.p, (const uint64_t *)g->out_info.p,
-                           D, flag.p);
-        LAUNCH_OK();
-        // sinks per W first, then each W's flagged ids (a counting iterator: no id array)
+        launch_at(st, grid(D), dim3(kB), k_sv_sink_flags, B.sym.p, g->out_info.p, D, flag.p);
         DevBuf<unsigned long long> cnt4(4), num(1);
         HIP_OK(hipMemsetAsync(cnt4.p, 0, 32, st));
-        hipLaunchKernelGGL(k_sv_sink_count, grid(D), dim3(kB), 0, st, (const uint8_t *)flag.p, D, cnt4.p);
-        LAUNCH_OK();
+        launch_at(st, grid(D), dim3(kB), k_sv_sink_count, flag.p, D, cnt4.p);
         unsigned long long hc4[4];
         d2h(ctx, hc4, cnt4.p, 32);
         DevBuf<uint8_t> f1(D ? D : 1);
@@ -619,12 +612,10 @@ SvView build_view(mcaat_graph *g, SvBufs &B, uint64_t *n_sinks) {
             per[c].alloc(hc4[c] ? hc4[c] : 1);
             ns += hc4[c];
             if (!hc4[c]) continue;
-            hipLaunchKernelGGL(k_sv_eq, grid(D), dim3(kB), 0, st, (const uint8_t *)flag.p, D, (uint8_t)(c + 1), f1.p);
-            LAUNCH_OK();
-            size_t tmp = 0;
-            HIP_OK(hipcub::DeviceSelect::Flagged(nullptr, tmp, ids, f1.p, per[c].p, num.p, (size_t)D, st));
-            DevBuf<uint8_t> t(tmp ? tmp : 1);
-            HIP_OK(hipcub::DeviceSelect::Flagged(t.p, tmp, ids, f1.p, per[c].p, num.p, (size_t)D, st));
+            launch_at(st, grid(D), dim3(kB), k_sv_eq, flag.p, D, c + 1, f1.p);
+            with_cub_temp([&](void *t, size_t &tmp) {
+                return hipcub::DeviceSelect::Flagged(t, tmp, ids, f1.p, per[c].p, num.p, (size_t)D, st);
+            });
         }
         sink_edge.alloc(ns ? ns : 1);
         uint64_t o = 0;
@@ -636,6 +627,8 @@ SvView build_view(mcaat_graph *g, SvBufs &B, uint64_t *n_sinks) {
     }
     v.nsink = ns;
     v.nU = v.nodes + ns;
+
+    // node-space bitmaps: the sinks' positions among the nodes, the nodes with an incoming edge
     const uint64_t nub = (v.nU + 63) / 64;
     B.sinkbm.alloc(nub + 1);
     B.hinbm.alloc(nub + 1);
@@ -646,63 +639,45 @@ SvView build_view(mcaat_graph *g, SvBufs &B, uint64_t *n_sinks) {
         DevBuf<uint32_t> cnt(v.nodes + 1), incl(v.nodes + 1);
         HIP_OK(hipMemsetAsync(cnt.p, 0, cnt.bytes(), st));
         if (ns) {
-            hipLaunchKernelGGL(k_sv_sink_pos, grid(ns), dim3(kB), 0, st, v, (const uint64_t *)g->key.p, k, (const uint64_t *)g->dir.p,
-                               g->dir_shift, (const uint64_t *)sink_edge.p, ns, a.p, cnt.p);
-            LAUNCH_OK();
-            hipLaunchKernelGGL(k_sv_mark_sinks, grid(ns), dim3(kB), 0, st, (const uint64_t *)a.p, ns, B.sinkbm.p, B.hinbm.p);
-            LAUNCH_OK();
+            launch_at(st, grid(ns), dim3(kB), k_sv_sink_pos, v, g->key.p, k, g->dir.p, g->dir_shift, sink_edge.p, ns, a.p, cnt.p);
+            launch_at(st, grid(ns), dim3(kB), k_sv_mark_sinks, a.p, ns, B.sinkbm.p, B.hinbm.p);
         }
-        size_t tmp = 0;
-        HIP_OK(hipcub::DeviceScan::InclusiveSum(nullptr, tmp, cnt.p, incl.p, (size_t)(v.nodes + 1), st));
-        {
-            DevBuf<uint8_t> t(tmp ? tmp : 1);
-            HIP_OK(hipcub::DeviceScan::InclusiveSum(t.p, tmp, cnt.p, incl.p, (size_t)(v.nodes + 1), st));
-        }
-        hipLaunchKernelGGL(k_sv_mark_nodes, grid(D), dim3(kB), 0, st, v, (const uint64_t *)g->in_info.p, (const uint32_t *)incl.p,
-                           B.hinbm.p);
-        LAUNCH_OK();
+        with_cub_temp([&](void *t, size_t &tmp) {
+            return hipcub::DeviceScan::InclusiveSum(t, tmp, cnt.p, incl.p, (size_t)(v.nodes + 1), st);
+        });
+        launch_at(st, grid(D), dim3(kB), k_sv_mark_nodes, v, g->in_info.p, incl.p, B.hinbm.p);
         HIP_OK(hipStreamSynchronize(st));
     }
     v.sinkbm = B.sinkbm.p;
     v.hinbm = B.hinbm.p;
-    // node-space rank structure
+
+    // node-space rank structure over the two bitmaps; samples
     B.ublk.alloc(2 * nub + 2);
     B.usb.alloc(2 * ((nub + 1023) / 1024) + 2);
-    uint64_t n_hin = 0;
     {
         DevBuf<uint32_t> raw(2 * nub + 2);
         DevBuf<uint64_t> abs(2 * nub + 2);
-        hipLaunchKernelGGL(k_sv_ublk_raw, grid(nub), dim3(kB), 0, st, (const uint64_t *)B.sinkbm.p, (const uint64_t *)B.hinbm.p, nub,
-                           raw.p);
-        LAUNCH_OK();
-        for (int kd = 0; kd < 2; ++kd) ex_scan(ctx, raw.p + (uint64_t)kd * nub, abs.p + (uint64_t)kd * nub, nub);
-        hipLaunchKernelGGL(k_sv_pack, grid(nub), dim3(kB), 0, st, (const uint64_t *)abs.p, nub, 2, B.ublk.p, B.usb.p);
-        LAUNCH_OK();
-        uint64_t a = 0;
-        uint32_t r = 0;
-        d2h(ctx, &a, abs.p + nub + nub - 1, 8);
-        d2h(ctx, &r, raw.p + nub + nub - 1, 4);
-        n_hin = a + r;
+        launch_at(st, grid(nub), dim3(kB), k_sv_ublk_raw, B.sinkbm.p, B.hinbm.p, nub, raw.p);
+        for (int kd = 0; kd < 2; ++kd)
+            excl_scan(st, (const uint32_t *)raw.p + (uint64_t)kd * nub, abs.p + (uint64_t)kd * nub, nub);
+        launch_at(st, grid(nub), dim3(kB), k_sv_pack, abs.p, nub, 2, B.ublk.p, B.usb.p);
+        v.ucount[1] = scan_total(abs.p + nub, raw.p + nub, nub);  // nodes with an incoming edge
     }
     v.ublk = B.ublk.p;
     v.usb = B.usb.p;
     v.ucount[0] = v.nodes;
-    v.ucount[1] = n_hin;
     for (int kd = 0; kd < 2; ++kd) {
         B.us[kd].alloc((v.ucount[kd] >> kSamp) + 1);
         v.us[kd] = B.us[kd].p;
     }
-    hipLaunchKernelGGL(k_sv_usamples, grid(nub), dim3(kB), 0, st, v, nub, B.us[0].p, B.us[1].p);
-    LAUNCH_OK();
+    launch_at(st, grid(nub), dim3(kB), k_sv_usamples, v, nub, B.us[0].p, B.us[1].p);
+
     // hinstart[c]: hin nodes before Ustart[c], the first U position whose label ends with c
     // (nodes whose label ends before c, plus the sinks of the W < c edges)
     {
         DevBuf<uint64_t> q(8), res(8);
-        std::vector<uint64_t> hq(5);
-        for (int c = 0; c <= 4; ++c) hq[c] = v.Estart[c];
-        h2d(ctx, q.p, hq.data(), 40);
-        hipLaunchKernelGGL(k_sv_nodes_before, dim3(1), dim3(64), 0, st, v, (const uint64_t *)q.p, res.p);
-        LAUNCH_OK();
+        h2d(ctx, q.p, v.Estart, 40);
+        launch_at(st, dim3(1), dim3(64), k_sv_nodes_before, v, q.p, res.p);
         std::vector<uint64_t> nbc(5), ustart(5);
         d2h(ctx, nbc.data(), res.p, 40);
         uint64_t sb = 0;
@@ -711,11 +686,8 @@ SvView build_view(mcaat_graph *g, SvBufs &B, uint64_t *n_sinks) {
             if (c < 4) sb += ns_c[c];
         }
         h2d(ctx, q.p, ustart.data(), 40);
-        hipLaunchKernelGGL(k_sv_hin_before, dim3(1), dim3(64), 0, st, v, (const uint64_t *)q.p, res.p);
-        LAUNCH_OK();
-        std::vector<uint64_t> hs(5);
-        d2h(ctx, hs.data(), res.p, 40);
-        for (int c = 0; c <= 4; ++c) v.hinstart[c] = hs[c];
+        launch_at(st, dim3(1), dim3(64), k_sv_hin_before, v, q.p, res.p);
+        d2h(ctx, v.hinstart, res.p, 40);
     }
     *n_sinks = ns;
     return v;
@@ -754,8 +726,7 @@ void graph_succinct_check(mcaat_graph *g, bool check, uint64_t *out, double *ms)
     if (check) {
         DevBuf<unsigned long long> bad(2);
         HIP_OK(hipMemsetAsync(bad.p, 0, 16, st));
-        hipLaunchKernelGGL(k_sv_check, dim3(grid_for(D, kB, (unsigned)ctx->n_cu * 16)), dim3(kB), 0, st, gv, v, bad.p);
-        LAUNCH_OK();
+        launch_at(st, dim3(grid_for(D, kB, (unsigned)ctx->n_cu * 16)), dim3(kB), k_sv_check, gv, v, bad.p);
         unsigned long long hb[2];
         d2h(ctx, hb, bad.p, 16);
         out[2] = hb[0];
@@ -771,8 +742,7 @@ void graph_succinct_check(mcaat_graph *g, bool check, uint64_t *out, double *ms)
         for (int rep = 0; rep < 2; ++rep) {
             HIP_OK(hipMemsetAsync(sum, 0, 8, st));
             HIP_OK(hipEventRecord(a, st));
-            hipLaunchKernelGGL(kern, gw, dim3(kB), 0, st, view, tips, sum);
-            LAUNCH_OK();
+            launch_at(st, gw, dim3(kB), kern, view, tips, sum);
             HIP_OK(hipEventRecord(b, st));
             best = std::min(best, elapsed());
         }

@@ -6,7 +6,7 @@
 // concatenated in rank order are the single-GPU edge array (edge ids bit-identical).
 #include <hipcub/hipcub.hpp>
 
-#include "internal.h"
+#include "cub_helpers.h"
 
 namespace mcaat {
 
@@ -218,10 +218,7 @@ uint64_t owner_major(mcaat_ctx *ctx, uint64_t n, int n_owners, const uint64_t *s
     if (ns > 0) HIP_OK(hipMemcpyAsync(sp.p, splits_host, 8 * (uint64_t)ns, hipMemcpyHostToDevice, st));
     HIP_OK(hipMemsetAsync(cur.p, 0, cur.bytes(), st));
     const unsigned grid = grid_for(n, kTile, (unsigned)ctx->n_cu * 8);
-    if (n) {
-        launch(grid, sp.p, ns, cur.p, 1);
-        LAUNCH_OK();
-    }
+    if (n) launch(grid, sp.p, ns, cur.p, 1);
     std::vector<unsigned long long> h(n_owners);
     HIP_OK(hipMemcpyAsync(h.data(), cur.p, 8 * (uint64_t)n_owners, hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
@@ -236,9 +233,29 @@ uint64_t owner_major(mcaat_ctx *ctx, uint64_t n, int n_owners, const uint64_t *s
     if (!total) return 0;
     HIP_OK(hipMemcpyAsync(cur.p, base.data(), 8 * (uint64_t)n_owners, hipMemcpyHostToDevice, st));
     launch(grid, sp.p, ns, cur.p, 0);
-    LAUNCH_OK();
     HIP_OK(hipStreamSynchronize(st));
     return total;
+}
+
+// (key, count) pairs sorted by key -> the counts of equal keys summed (keys_out, sums_out) -> the
+// number of distinct keys, read on the host. sums (edges_reduce) is allocated here, where its
+// caller had it; spent (canon_reduce's widened counts) is released once the sort is queued.
+uint64_t sort_reduce(hipStream_t st, int k, const uint64_t *keys, const uint32_t *cnt, uint64_t n, uint64_t *keys_out,
+                     uint32_t *sums_out, DevBuf<uint32_t> *sums, DevBuf<uint32_t> *spent) {
+    DevBuf<uint64_t> sk(n);
+    DevBuf<uint32_t> sc(n);
+    if (sums) {
+        sums->alloc(n);
+        sums_out = sums->p;
+    }
+    DevBuf<unsigned long long> nrun(1);
+    sort_pairs(st, keys, sk.p, cnt, sc.p, n, 2 * (k + 1));
+    if (spent) spent->release();
+    with_cub_temp([&](void *t, size_t &tmp) {
+        return hipcub::DeviceReduce::ReduceByKey(t, tmp, sk.p, keys_out, sc.p, sums_out, nrun.p, hipcub::Sum(), (size_t)n,
+                                                 st);
+    });
+    return read_counter(st, nrun.p);
 }
 
 }  // namespace
@@ -249,11 +266,9 @@ void counts_histogram(mcaat_ctx *ctx, const CountResult &c, int k, int bits, uin
     const int nbins = 1 << bits;
     DevBuf<unsigned long long> h(nbins);
     HIP_OK(hipMemsetAsync(h.p, 0, h.bytes(), st));
-    if (c.n) {
-        hipLaunchKernelGGL(k_boss_hist, dim3(grid_for(c.n, kBlock, (unsigned)ctx->n_cu * 8)), dim3(kBlock),
-                           4 * nbins, st, c.keys.p, c.counts.p, c.n, k, shift, nbins, h.p);
-        LAUNCH_OK();
-    }
+    if (c.n)
+        launch_lds(st, dim3(grid_for(c.n, kBlock, (unsigned)ctx->n_cu * 8)), dim3(kBlock), 4 * nbins, k_boss_hist, c.keys.p,
+                   c.counts.p, c.n, k, shift, nbins, h.p);
     HIP_OK(hipMemcpyAsync(hist_host, h.p, 8 * (uint64_t)nbins, hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
 }
@@ -261,63 +276,20 @@ void counts_histogram(mcaat_ctx *ctx, const CountResult &c, int k, int bits, uin
 void counts_partition(mcaat_ctx *ctx, const CountResult &c, int k, int n_owners, const uint64_t *splits_host,
                       uint64_t *sizes_host, uint64_t *okeys, uint32_t *ocnt, uint64_t cap) {
     hipStream_t st = ctx->stream;
-    const int ns = n_owners - 1;
-    DevBuf<uint64_t> sp(ns > 0 ? ns : 1);
-    DevBuf<unsigned long long> cur(n_owners);
-    if (ns > 0) HIP_OK(hipMemcpyAsync(sp.p, splits_host, 8 * (uint64_t)ns, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemsetAsync(cur.p, 0, cur.bytes(), st));
-    const unsigned grid = grid_for(c.n, kTile, (unsigned)ctx->n_cu * 8);
-    if (c.n) {
-        hipLaunchKernelGGL(k_partition, dim3(grid), dim3(kBlock), 0, st, c.keys.p, c.counts.p, c.n, k, sp.p, ns, cur.p,
-                           (uint64_t *)nullptr, (uint32_t *)nullptr, 1);
-        LAUNCH_OK();
-    }
-    std::vector<unsigned long long> h(n_owners);
-    HIP_OK(hipMemcpyAsync(h.data(), cur.p, 8 * (uint64_t)n_owners, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    uint64_t total = 0;
-    std::vector<unsigned long long> base(n_owners);
-    for (int o = 0; o < n_owners; ++o) {
-        base[o] = total;
-        sizes_host[o] = h[o];
-        total += h[o];
-    }
-    if (total > cap) throw Error(MCAAT_E_CAPACITY, "partition: output buffers smaller than the oriented edges");
-    if (!total) return;
-    HIP_OK(hipMemcpyAsync(cur.p, base.data(), 8 * (uint64_t)n_owners, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_partition, dim3(grid), dim3(kBlock), 0, st, c.keys.p, c.counts.p, c.n, k, sp.p, ns, cur.p,
-                       okeys, ocnt, 0);
-    LAUNCH_OK();
-    HIP_OK(hipStreamSynchronize(st));
+    owner_major(ctx, c.n, n_owners, splits_host, sizes_host, cap,
+                [&](unsigned grid, const uint64_t *sp, int ns, unsigned long long *cur, int count_only) {
+                    launch_at(st, dim3(grid), dim3(kBlock), k_partition, c.keys.p, c.counts.p, c.n, k, sp, ns, cur,
+                              count_only ? nullptr : okeys, count_only ? nullptr : ocnt, count_only);
+                });
 }
 
 uint64_t edges_reduce(mcaat_ctx *ctx, int k, const uint64_t *keys, const uint32_t *cnt, uint64_t n, uint64_t *keys_out,
                       uint16_t *mult_out) {
     if (!n) return 0;
     hipStream_t st = ctx->stream;
-    const int E = k + 1;
-    DevBuf<uint64_t> sk(n);
-    DevBuf<uint32_t> sc(n), agg(n);
-    DevBuf<unsigned long long> nrun(1);
-    size_t tmp = 0;
-    HIP_OK(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp, keys, sk.p, cnt, sc.p, (size_t)n, 0, 2 * E, st));
-    {
-        DevBuf<uint8_t> t(tmp);
-        HIP_OK(hipcub::DeviceRadixSort::SortPairs(t.p, tmp, keys, sk.p, cnt, sc.p, (size_t)n, 0, 2 * E, st));
-    }
-    tmp = 0;
-    HIP_OK(hipcub::DeviceReduce::ReduceByKey(nullptr, tmp, sk.p, keys_out, sc.p, agg.p, nrun.p, hipcub::Sum(),
-                                             (size_t)n, st));
-    {
-        DevBuf<uint8_t> t(tmp);
-        HIP_OK(hipcub::DeviceReduce::ReduceByKey(t.p, tmp, sk.p, keys_out, sc.p, agg.p, nrun.p, hipcub::Sum(),
-                                                 (size_t)n, st));
-    }
-    unsigned long long u = 0;
-    HIP_OK(hipMemcpyAsync(&u, nrun.p, 8, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    hipLaunchKernelGGL(k_saturate, dim3(grid_for(u, kBlock)), dim3(kBlock), 0, st, agg.p, (uint64_t)u, mult_out);
-    LAUNCH_OK();
+    DevBuf<uint32_t> agg;
+    const uint64_t u = sort_reduce(st, k, keys, cnt, n, keys_out, nullptr, &agg, nullptr);
+    launch_at(st, dim3(grid_for(u, kBlock)), dim3(kBlock), k_saturate, agg.p, u, mult_out);
     HIP_OK(hipStreamSynchronize(st));
     return u;
 }
@@ -327,8 +299,8 @@ uint64_t counts_partition_canon(mcaat_ctx *ctx, const CountResult &c, int k, int
     hipStream_t st = ctx->stream;
     return owner_major(ctx, c.n, n_owners, splits_host, sizes_host, cap,
                        [&](unsigned grid, const uint64_t *sp, int ns, unsigned long long *cur, int count_only) {
-                           hipLaunchKernelGGL(k_partition_canon, dim3(grid), dim3(kBlock), 0, st, c.keys.p, c.counts.p,
-                                              c.n, k, sp, ns, cur, okeys, ocnt, count_only);
+                           launch_at(st, dim3(grid), dim3(kBlock), k_partition_canon, c.keys.p, c.counts.p, c.n, k, sp,
+                                     ns, cur, okeys, ocnt, count_only);
                        });
 }
 
@@ -336,32 +308,9 @@ uint64_t canon_reduce(mcaat_ctx *ctx, int k, const uint64_t *keys, const uint16_
                       uint32_t *tot_out) {
     if (!n) return 0;
     hipStream_t st = ctx->stream;
-    const int E = k + 1;
     DevBuf<uint32_t> cnt(n);
-    hipLaunchKernelGGL(k_widen16, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, st, cnt16, n, cnt.p);
-    LAUNCH_OK();
-    DevBuf<uint64_t> sk(n);
-    DevBuf<uint32_t> sc(n);
-    DevBuf<unsigned long long> nrun(1);
-    size_t tmp = 0;
-    HIP_OK(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp, keys, sk.p, cnt.p, sc.p, (size_t)n, 0, 2 * E, st));
-    {
-        DevBuf<uint8_t> t(tmp);
-        HIP_OK(hipcub::DeviceRadixSort::SortPairs(t.p, tmp, keys, sk.p, cnt.p, sc.p, (size_t)n, 0, 2 * E, st));
-    }
-    cnt.release();
-    tmp = 0;
-    HIP_OK(hipcub::DeviceReduce::ReduceByKey(nullptr, tmp, sk.p, keys_out, sc.p, tot_out, nrun.p, hipcub::Sum(),
-                                             (size_t)n, st));
-    {
-        DevBuf<uint8_t> t(tmp);
-        HIP_OK(hipcub::DeviceReduce::ReduceByKey(t.p, tmp, sk.p, keys_out, sc.p, tot_out, nrun.p, hipcub::Sum(),
-                                                 (size_t)n, st));
-    }
-    unsigned long long u = 0;
-    HIP_OK(hipMemcpyAsync(&u, nrun.p, 8, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    return u;
+    launch_at(st, dim3(grid_for(n, kBlock)), dim3(kBlock), k_widen16, cnt16, n, cnt.p);
+    return sort_reduce(st, k, keys, cnt.p, n, keys_out, tot_out, nullptr, &cnt);
 }
 
 uint64_t route_oriented(mcaat_ctx *ctx, int k, const uint64_t *keys, const uint32_t *tot, uint64_t n, int n_owners,
@@ -369,8 +318,8 @@ uint64_t route_oriented(mcaat_ctx *ctx, int k, const uint64_t *keys, const uint3
     hipStream_t st = ctx->stream;
     return owner_major(ctx, n, n_owners, splits_host, sizes_host, cap,
                        [&](unsigned grid, const uint64_t *sp, int ns, unsigned long long *cur, int count_only) {
-                           hipLaunchKernelGGL(k_route_oriented, dim3(grid), dim3(kBlock), 0, st, keys, tot, n, k, sp,
-                                              ns, cur, okeys, omult, count_only);
+                           launch_at(st, dim3(grid), dim3(kBlock), k_route_oriented, keys, tot, n, k, sp, ns, cur, okeys,
+                                     omult, count_only);
                        });
 }
 
@@ -378,10 +327,7 @@ void sort_oriented(mcaat_ctx *ctx, int k, const uint64_t *keys, const uint16_t *
                    uint16_t *mult_out) {
     if (!n) return;
     hipStream_t st = ctx->stream;
-    size_t tmp = 0;
-    HIP_OK(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp, keys, keys_out, mult, mult_out, (size_t)n, 0, 2 * (k + 1), st));
-    DevBuf<uint8_t> t(tmp);
-    HIP_OK(hipcub::DeviceRadixSort::SortPairs(t.p, tmp, keys, keys_out, mult, mult_out, (size_t)n, 0, 2 * (k + 1), st));
+    sort_pairs(st, keys, keys_out, mult, mult_out, n, 2 * (k + 1));
     HIP_OK(hipStreamSynchronize(st));
 }
 

@@ -48,6 +48,7 @@
 #include <map>
 
 #include "comm.h"
+#include "cub_helpers.h"
 
 namespace mcaat {
 
@@ -71,11 +72,6 @@ constexpr uint64_t kPad = kNo - 1;  // an unused successor slot of a branch
 // unary chains meet (walks claim it by compare-and-swap)
 constexpr uint64_t kChain = 1ULL << 59, kMergeW = 1ULL << 58;
 __device__ __forceinline__ bool is_chain(uint64_t v) { return v < kPad && (v & kChain) && !(v & (kRef | (1ULL << 61))); }
-
-bool verbose() {
-    static const bool v = getenv("MCAAT_VERBOSE") && getenv("MCAAT_VERBOSE")[0] == '1';
-    return v;
-}
 
 // ---------------------------------------------------------------- owners
 struct Owners {  // N <= 64 (Comm limits)
@@ -1856,10 +1852,7 @@ struct ShardCf {
         HIP_OK(hipMemsetAsync(b.pc.p + nw, 0, 8, st));
         if (nw) {
             run(nw, k_word_popc64, bm, nw, b.pc.p);
-            size_t tmp = 0;
-            HIP_OK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, b.pc.p, b.wpre.p, (size_t)(nw + 1), st));
-            DevBuf<uint8_t> t(tmp);
-            HIP_OK(hipcub::DeviceScan::ExclusiveSum(t.p, tmp, b.pc.p, b.wpre.p, (size_t)(nw + 1), st));
+            excl_scan(st, b.pc.p, b.wpre.p, nw + 1);
             d2h(ctx, &b.total, b.wpre.p + nw, 8);
         }
         return b;
@@ -1905,10 +1898,9 @@ struct ShardCf {
     // in[j] where flags[j] != 0, in order (hipcub select); returns the count
     uint64_t select(const uint64_t *in, const uint8_t *flags, uint64_t m, uint64_t *sel) {
         DevBuf<unsigned long long> num(1);
-        size_t tmp = 0;
-        HIP_OK(hipcub::DeviceSelect::Flagged(nullptr, tmp, in, flags, sel, num.p, (size_t)m, st));
-        DevBuf<uint8_t> t(tmp ? tmp : 1);
-        HIP_OK(hipcub::DeviceSelect::Flagged(t.p, tmp, in, flags, sel, num.p, (size_t)m, st));
+        with_cub_temp([&](void *t, size_t &tmp) {
+            return hipcub::DeviceSelect::Flagged(t, tmp, in, flags, sel, num.p, (size_t)m, st);
+        });
         return read_u64(ctx, num.p);
     }
 

@@ -67,7 +67,6 @@ KNOBS = {
     "split_eight_ways_big": {"nc.split_first": 3, "nc.big_table": 1, "nc.edge_cap": 300},
     # level-3 buckets through the 256-thread LDS sort, the 1024-thread one, and the radix fallback
     "sort_mid": {"sort.msd": 1, "sort.wave_limit": 0},
-    "sort_mid_occ5": {"sort.msd": 1, "sort.wave_limit": 0, "sort.mid_occ": 5},
     # the 128-thread level-3 stage forwarding everything to the 256-thread one, and skipped
     "sort_small_fwd": {"sort.msd": 1, "sort.wave_limit": 0, "sort.small_mid": 1, "sort.small_limit": 0},
     "sort_small_on": {"sort.msd": 1, "sort.wave_limit": 0, "sort.small_mid": 1},
@@ -190,7 +189,7 @@ def test_retired_knobs_are_unknown(gpu_ctx):
     """The knobs whose paths are gone answer MCAAT_E_INVALID (-1) like any unknown name; a
     surviving knob is still accepted, the two test handles on live sdbg_build paths among them."""
     for name in ("cf.pull_flags", "cf.recount", "cf.walk_budget", "cf.dls_persist", "cf.scan_u", "cf.prep_batch",
-                 "sort.mid_counting"):
+                 "sort.mid_counting", "sort.mid_occ"):
         with pytest.raises(M.McaatError) as err:
             gpu_ctx.set_knob(name, 1)
         assert err.value.code == -1, name
