@@ -332,6 +332,19 @@ int mcaat_cycle_finder_comm(mcaat_graph *g, mcaat_comm *comm, const mcaat_cf_par
  * Replaces cycle_finder.cpp:346-492 over a graph split by ranges. */
 int mcaat_graph_shard_info(const mcaat_graph *g, int *sharded, uint64_t *first, uint64_t *n_local);
 int mcaat_graph_unshard(mcaat_graph *g, mcaat_comm *comm);
+/* Host-only: the rule by which mcaat_build_graph_sharded cuts the BOSS key space into `world`
+ * owner ranges (csrc/splits.h, the functions the build runs). *bits = min(12, 2(k-1)) histogram
+ * bits (the top bits of the 2(k+1)-bit key); hist[2^bits] the summed histogram; splits[world-1]
+ * ascending bin edges, each a multiple of 16 (edges sharing key >> 4 never straddle two owners):
+ * owners 0..o-1 end after the first bin whose running sum reaches total * o / world. hist NULL:
+ * only *bits is reported. MCAAT_E_INVALID unless 2 <= k <= 30 and 1 <= world <= 64. No GPU. */
+int mcaat_shard_splits(int k, int world, const uint64_t *hist, uint64_t *splits, int *bits);
+/* Check-only: the raw adjacency words (csrc/common.h: out_info, in_info) of the global edge ids
+ * [first, first + count), either output NULL to skip it. On a sharded graph the range must lie
+ * inside this rank's [first, first + n_local) of mcaat_graph_shard_info (MCAAT_E_INVALID
+ * otherwise); no collective call. */
+int mcaat_graph_adjacency_words(const mcaat_graph *g, uint64_t first, uint64_t count, uint64_t *out_info,
+                                uint64_t *in_info);
 
 /* ---- measurement -------------------------------------------------------------
  * Per-stage device time of the last build/cycle_finder call on this ctx, measured

@@ -23,6 +23,8 @@ from .lib import (  # noqa: F401
     device_count,
     load_library,
     preload,
+    shard_hist_bits,
+    shard_splits,
     synth_arrays,
     synth_genome_host,
     synth_host,

@@ -12,6 +12,7 @@
 #include "internal.h"
 #include "comm.h"
 #include "desc_canon.h"
+#include "splits.h"
 #include "synth.h"
 
 using namespace mcaat;
@@ -904,6 +905,19 @@ int mcaat_graph_succinct_check(mcaat_graph *g, int check, uint64_t *out, double 
     });
 }
 
+int mcaat_graph_adjacency_words(const mcaat_graph *g, uint64_t first, uint64_t count, uint64_t *out_info,
+                                uint64_t *in_info) {
+    return guarded([&] {
+        require(g != nullptr, "null argument");
+        const uint64_t lo = g->sharded ? g->id_lo : 0, n = g->sharded ? g->D_local : g->D;
+        require(first >= lo && first - lo <= n && count <= n - (first - lo), "edge range outside this rank's edges");
+        if (!count) return;
+        mcaat::bind(g->ctx);
+        if (out_info) HIP_OK(hipMemcpy(out_info, g->out_info.p + (first - lo), 8 * count, hipMemcpyDeviceToHost));
+        if (in_info) HIP_OK(hipMemcpy(in_info, g->in_info.p + (first - lo), 8 * count, hipMemcpyDeviceToHost));
+    });
+}
+
 int mcaat_graph_save(const mcaat_graph *g, const char *path) {
     return guarded([&] {
         require(g && path, "null argument");
@@ -1138,6 +1152,19 @@ int mcaat_desc_sub(uint64_t w1, int l2_bits, int *live, uint32_t *sub) {
         require(l2_bits >= 0 && l2_bits <= kHBits, "l2_bits must be in [0, 14]");
         *live = desc_live(w1) ? 1 : 0;
         *sub = desc_sub(w1, l2_bits);
+    });
+}
+
+int mcaat_shard_splits(int k, int world, const uint64_t *hist, uint64_t *splits, int *bits) {
+    return guarded([&] {
+        require(k >= 2 && k <= kMaxK, "k must be in [2, 30]");
+        require(world >= 1 && world <= 64, "world must be in [1, 64]");
+        const int b = shard_hist_bits(k);
+        if (bits) *bits = b;
+        if (!hist) return;
+        require(splits != nullptr || world == 1, "null argument");
+        const std::vector<uint64_t> s = choose_splits(std::vector<uint64_t>(hist, hist + (1u << b)), world, 2 * (k + 1));
+        for (size_t i = 0; i < s.size(); ++i) splits[i] = s[i];
     });
 }
 

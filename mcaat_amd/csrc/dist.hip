@@ -22,37 +22,9 @@
 #include <vector>
 
 #include "comm.h"
+#include "splits.h"
 
 namespace mcaat {
-
-namespace {
-
-constexpr int kHistBits = 12;
-
-// world-1 ascending split points at histogram-bin edges with equal weight (owner o takes
-// keys in [splits[o-1], splits[o])); the same rule as shard.choose_splits
-std::vector<uint64_t> choose_splits(const std::vector<uint64_t> &hist, int world, int key_bits) {
-    const int nb = (int)hist.size();
-    int bits = 0;
-    while ((1 << bits) < nb) ++bits;
-    const int shift = key_bits - bits;
-    std::vector<double> cum(nb);
-    double acc = 0;
-    for (int i = 0; i < nb; ++i) cum[i] = acc += (double)hist[i];
-    const double total = nb ? cum[nb - 1] : 0.0;
-    std::vector<uint64_t> out;
-    int prev = 0;
-    for (int o = 1; o < world; ++o) {
-        int b = nb;
-        if (total > 0) b = (int)(std::lower_bound(cum.begin(), cum.end(), total * o / world) - cum.begin()) + 1;
-        b = std::min(std::max(b, prev), nb);
-        out.push_back((uint64_t)b << shift);
-        prev = b;
-    }
-    return out;
-}
-
-}  // namespace
 
 // Round 4 (default; knob dist.desc=0 keeps the count exchange below): pass A's super-k-mer
 // descriptors go to the owner of their L1 bucket. Every occurrence of a canonical edge has
@@ -185,8 +157,10 @@ void build_graph_sharded(mcaat_ctx *ctx, Comm &comm, const mcaat_reads *r, int k
         timer.mark("node_counter");
     }
 
-    std::vector<uint64_t> hist(1u << kHistBits);
-    counts_histogram(ctx, c, k, kHistBits, hist.data());
+    // splits at group boundaries (multiples of 16) at every k: splits.h
+    const int hist_bits = shard_hist_bits(k);
+    std::vector<uint64_t> hist(1u << hist_bits);
+    counts_histogram(ctx, c, k, hist_bits, hist.data());
     {
         const std::vector<uint64_t> all = comm.allgather_vec(hist);
         std::fill(hist.begin(), hist.end(), 0);

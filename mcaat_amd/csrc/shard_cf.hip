@@ -1753,6 +1753,7 @@ void adjacency_by_messages(mcaat_ctx *ctx, Comm &comm, mcaat_graph *g) {
         L.run(m, k_adj_store, q.p, i0, m, g->out_info.p, g->in_info.p);
     }
     kt.stop();
+    ctx->kstats["shard_adj_exchanges"].launches = rt.rounds;  // two per chunk: the queries, the answers
     if (verbose())
         fprintf(stderr, "[mcaat] shard %d: adjacency of %llu edges, %llu exchanges, %llu queries\n", comm.rank,
                 (unsigned long long)n, (unsigned long long)rt.rounds, (unsigned long long)rt.records);

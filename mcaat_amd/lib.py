@@ -144,6 +144,8 @@ SIGNATURES = {
     "mcaat_arena_usage": (C.c_int, [C.c_void_p, C.c_int, _u64p, _u64p, _u64p]),
     "mcaat_graph_shard_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), _u64p, _u64p]),
     "mcaat_graph_unshard": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mcaat_shard_splits": (C.c_int, [C.c_int, C.c_int, _u64p, _u64p, C.POINTER(C.c_int)]),
+    "mcaat_graph_adjacency_words": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, _u64p, _u64p]),
 }
 
 _lib: Optional[C.CDLL] = None
@@ -187,6 +189,26 @@ def desc_canonical(w0: int, w1: int, E: int) -> Tuple[int, int]:
     dst = (C.c_uint64 * 2)()
     _check(load_library().mcaat_desc_canonical(src, int(E), dst))
     return int(dst[0]), int(dst[1])
+
+
+def shard_hist_bits(k: int) -> int:
+    """Histogram bits of the sharded build's key-range rule at k (mcaat_shard_splits; host only)."""
+    bits = C.c_int(0)
+    _check(load_library().mcaat_shard_splits(int(k), 1, None, None, C.byref(bits)))
+    return bits.value
+
+
+def shard_splits(k: int, world: int, hist: np.ndarray) -> np.ndarray:
+    """The world-1 BOSS-key splits the sharded build cuts from the summed histogram `hist`
+    (2^shard_hist_bits(k) bins; mcaat_shard_splits; host only)."""
+    bits = C.c_int(0)
+    _check(load_library().mcaat_shard_splits(int(k), int(world), None, None, C.byref(bits)))
+    hist = np.ascontiguousarray(hist, dtype=np.uint64)
+    if hist.size != 1 << bits.value:
+        raise ValueError(f"the histogram at k = {k} has {1 << bits.value} bins, got {hist.size}")
+    splits = np.zeros(max(world - 1, 1), dtype=np.uint64)
+    _check(load_library().mcaat_shard_splits(int(k), int(world), _ptr(hist, _u64p), _ptr(splits, _u64p), None))
+    return splits[: world - 1]
 
 
 def desc_sub(w1: int, l2_bits: int) -> Tuple[bool, int]:
@@ -712,6 +734,14 @@ class Graph:
         _check(self.ctx._lib.mcaat_graph_neighbors(self.h, _ptr(ids, _u64p), ids.size, int(incoming),
                                                    _ptr(out, _u64p), _ptr(cnt, _i32p)))
         return out[: 4 * ids.size].reshape(-1, 4), cnt[: ids.size]
+
+    def adjacency_words(self, first: int, count: int) -> Tuple[np.ndarray, np.ndarray]:
+        """The raw (out_info, in_info) words of the global edge ids [first, first+count); on a
+        sharded graph inside this rank's range, no collective (mcaat_graph_adjacency_words)."""
+        oi = np.zeros(max(count, 1), dtype=np.uint64)
+        ii = np.zeros(max(count, 1), dtype=np.uint64)
+        _check(self.ctx._lib.mcaat_graph_adjacency_words(self.h, first, count, _ptr(oi, _u64p), _ptr(ii, _u64p)))
+        return oi[:count], ii[:count]
 
     def gather(self, ids: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
         """(keys, mult) of the given edge ids (mcaat_graph_gather)."""

@@ -73,3 +73,13 @@ def test_sanitized_idmap(driver):
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=1", UBSAN_OPTIONS="print_stacktrace=1")
     p = subprocess.run([os.path.join(SAN, "build", "idmap_test")], capture_output=True, text=True, timeout=300, env=env)
     assert p.returncode == 0 and "idmap ok" in p.stdout, (p.stdout + p.stderr)[-3000:]
+
+
+def test_sanitized_shard_splits(driver):
+    """The sharded build's key-range rule (csrc/splits.h) at every k in 2..30 and every world in
+    1..64 on seeded histograms (tests/sanitize/splits_test.cpp, same sanitizer build): no shift out
+    of range, and the splits are ascending multiples of 16 inside the key space."""
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=1", UBSAN_OPTIONS="print_stacktrace=1")
+    p = subprocess.run([os.path.join(SAN, "build", "splits_test")], capture_output=True, text=True, timeout=300, env=env)
+    assert p.returncode == 0 and "splits ok" in p.stdout, (p.stdout + p.stderr)[-3000:]
+    assert "runtime error" not in p.stderr, p.stderr[-3000:]

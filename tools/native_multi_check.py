@@ -10,6 +10,9 @@ usage: native_multi_check.py --world N --rank R --comm shm|rccl --name /x [--rea
        native_multi_check.py ... --config c3 --digest FILE   (a bench config at full size: the
            rank writes checksums of its graph and results instead of comparing in-process)
        native_multi_check.py --single --config c3 --digest FILE   (the one-GPU path's checksums)
+       native_multi_check.py ... --input FILE --k K [--fastx FASTQ]   (the rank's own reads from FILE;
+           the sharded adjacency words, the gathered graph and CycleFinder against the CPU oracle's
+           results in FILE, never against the one-GPU path: input_mode)
 """
 import argparse
 import os
@@ -50,6 +53,149 @@ def checksums(g, res) -> dict:
 XR_STAGES = ("build", "tips_filter", "peel", "recount", "candidates", "dls", "find_cycle")
 
 
+def decode_adjacency(oi: np.ndarray, ii: np.ndarray):
+    """Raw adjacency words -> (out[n, 4], out counts, in[n, 4], in counts), unused slots 0, by
+    the layout documented in csrc/common.h. out_info: bits 0..39 the first id, bits 40..43 the
+    mask; the out-edges are the popcount(mask) consecutive ids from it, listed descending.
+    in_info: bits 0..39 the group start, bits 40..55 the positions in the group, ascending. With
+    an empty mask the id bits mean nothing and are not read. More than four positions: count 99."""
+    u = np.uint64
+    n = oi.size
+    idx = u((1 << 40) - 1)
+    j = np.arange(4, dtype=np.int64)[None, :]
+    om = ((oi >> u(40)) & u(0xF)).astype(np.int64)
+    oc = ((om & 1) + ((om >> 1) & 1) + ((om >> 2) & 1) + ((om >> 3) & 1)).astype(np.int32)
+    first = (oi & idx).astype(np.int64)[:, None]
+    out = np.where(j < oc[:, None], first + oc[:, None] - 1 - j, 0).astype(np.uint64)
+    im = ((ii >> u(40)) & u(0xFFFF)).astype(np.int64)
+    lo = (ii & idx).astype(np.int64)
+    inn = np.zeros((n, 4), dtype=np.uint64)
+    ic = np.zeros(n, dtype=np.int32)
+    for b in range(16):
+        sel = np.nonzero((im >> b) & 1)[0]
+        fit = sel[ic[sel] < 4]
+        inn[fit, ic[fit]] = (lo[fit] + b).astype(np.uint64)
+        ic[sel] += 1
+    ic[ic > 4] = 99
+    return out, oc, inn, ic
+
+
+def input_mode(a, make_comm) -> int:
+    """--input FILE --k K: every comparison against the CPU oracle's results in FILE (written by
+    tests/test_sharded_k_sweep.py): this rank's reads (packed_<r>, offsets_<r>; --fastx: its
+    part of that FASTQ file instead), keys, mult, the oracle's neighbours of every edge of the fresh
+    graph (out, out_n, in, in_n) and, optionally, its CycleFinder results at threads = 1 (cf_params,
+    cf_valid, cf_stats, cf_candidates, cf_buckets, cf_entries as JSON text)."""
+    import json
+
+    z = np.load(a.input)
+    k, R = a.k, a.rank
+    want = (z["out"], z["out_n"], z["in"], z["in_n"])
+    okeys, omult = z["keys"], z["mult"]
+    D = okeys.size
+    ctx = M.Context(0)
+    for kv in a.knob:
+        kn, kval = kv.split("=")
+        ctx.set_knob(kn, int(kval))
+    comm = make_comm(ctx)
+    bad = []
+
+    def check(cond, what):
+        if not cond:
+            bad.append(what)
+            print(f"rank {R}: MISMATCH {what}", flush=True)
+
+    def check_nbrs(got, first, words, tag):
+        """got = (out, out counts, in, in counts) of the ids [first, first + n); names the first
+        edge that differs, with its raw word when the lists came from one."""
+        n = got[1].size
+        for (ids, cnt), wi, wc, which in ((got[0:2], want[0], want[1], "out"), (got[2:4], want[2], want[3], "in")):
+            wi, wc = wi[first:first + n], wc[first:first + n]
+            used = np.arange(4)[None, :] < wc[:, None]
+            diff = (cnt != wc) | (np.where(used, ids, 0) != np.where(used, wi, 0)).any(axis=1)
+            if diff.any():
+                i = int(np.nonzero(diff)[0][0])
+                word = f" word {int(words[1 if which == 'in' else 0][i]):#018x}" if words is not None else ""
+                check(False, f"{tag}: {which}-neighbours of edge {first + i} (key {int(okeys[first + i]):#x}):{word} "
+                             f"got {ids[i, :min(max(int(cnt[i]), 0), 4)].tolist()} (count {int(cnt[i])}), "
+                             f"oracle {wi[i, :wc[i]].tolist()}; {int(diff.sum())} edges differ")
+
+    def load_reads():
+        if a.fastx:
+            rd = M.Reads.from_fastx_part(ctx, [a.fastx], R, a.world)
+            print(f"rank {R}: reads_info={rd.info()}", flush=True)
+            return rd
+        return M.Reads.from_host(ctx, z[f"packed_{R}"], z[f"offsets_{R}"])
+
+    mine = load_reads()
+    g = M.Graph.build_sharded(ctx, comm, mine, k)
+    sharded, first, n_local = g.shard_info()
+    # adj_exchanges: the message adjacency's exchanges (dist.adj_ranges=0: two per chunk of
+    # max(1024, dist.adj_chunk) edges, as many chunks as the rank with the most edges needs; 0 otherwise)
+    print(f"rank {R}: sharded={sharded} first={first} n_local={n_local} "
+          f"adj_exchanges={ctx.kernel_timing('shard_adj_exchanges')[1]}", flush=True)
+    check(g.size == D, f"D {g.size} vs the oracle's {D}")
+    if sharded:  # a range that leaves this rank's [first, first + n_local) is refused, not gathered
+        for a0, cnt in ((first, n_local + 1), (first + n_local, 1)) + (((first - 1, 1),) if first else ()):
+            try:
+                g.adjacency_words(a0, cnt)
+                check(False, f"adjacency_words({a0}, {cnt}) outside the shard was not refused")
+            except M.McaatError as e:
+                check(e.code == -1, f"adjacency_words outside the shard: status {e.code}, not MCAAT_E_INVALID")
+    if sharded and not bad:  # while still sharded: this rank's own words, as the shard's adjacency built them
+        check(first + n_local <= D, "shard range past D")
+        oi, ii = g.adjacency_words(first, n_local)
+        check_nbrs(decode_adjacency(oi, ii), first, (oi, ii), "sharded words")
+    g.unshard(comm)
+    keys, mult, valid = g.download()
+    check(np.array_equal(keys, okeys), "keys")
+    check(np.array_equal(mult, omult), "multiplicities")
+    check(bool(valid.all()), "valid bits of the fresh graph")
+    if not bad:
+        ids = np.arange(D, dtype=np.uint64)
+        o, oc = g.neighbors(ids, incoming=False)
+        p, pc = g.neighbors(ids, incoming=True)
+        check_nbrs((o, oc, p, pc), 0, None, "neighbors() after unshard")
+        oi, ii = g.adjacency_words(0, D)
+        check_nbrs(decode_adjacency(oi, ii), 0, (oi, ii), "words after unshard")
+    g.free()
+
+    same = True
+    if "cf_stats" in z.files:
+        prm = M.CfParams(**json.loads(z["cf_params"].tobytes().decode()))
+        entries = json.loads(z["cf_entries"].tobytes().decode())
+        g = M.Graph.build_sharded(ctx, comm, mine, k)
+        ctx.stage_times()
+        t0 = time.time()
+        res = g.cycle_finder(prm, comm=comm)
+        print(f"rank {R}: cycle_finder {time.time() - t0:.2f} s, stages ms "
+              f"{ {kk: round(vv, 1) for kk, vv in ctx.stage_times().items()} }, collectives "
+              f"{ {st: ctx.kernel_timing('xr_' + st)[1] for st in XR_STAGES} }", flush=True)
+        g.unshard(comm)
+        keys, mult, valid = g.download()
+        g.free()
+        check(np.array_equal(keys, okeys) and np.array_equal(mult, omult), "keys / multiplicities of the second build")
+        check(np.array_equal(valid, z["cf_valid"]),
+              f"valid bits after CycleFinder ({int((valid != z['cf_valid']).sum())} differ)")
+        check(list(res.stats[:6]) == z["cf_stats"].tolist(), f"stats {res.stats[:6]} vs {z['cf_stats'].tolist()}")
+        check(list(res.candidates) == z["cf_candidates"].tolist(), "candidates")
+        check(list(res.buckets) == z["cf_buckets"].tolist(), "buckets")
+        check([[s, [list(c) for c in cyc]] for s, cyc in res.entries] == entries,
+              f"entries ({len(res.entries)} vs {len(entries)})")
+        digest = repr((res.entries, res.stats[:6], list(res.candidates), list(res.buckets))).encode()
+        same = len(set(comm.allgather_bytes(digest))) == 1
+        check(same, "the ranks' CycleFinder results differ")
+        print(f"rank {R}: entries={len(res.entries)} cycles={res.stats[5]} ranks_agree={same}", flush=True)
+    mine.free()
+    comm.barrier()
+    comm.close()
+    ctx.close()
+    if not bad:
+        print("NATIVE_MULTI_OK", flush=True)
+        return 0
+    return 1
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--world", type=int, required=True)
@@ -67,6 +213,9 @@ def main() -> int:
     ap.add_argument("--repeat", type=int, default=1, help="--config: sharded builds in a row (stages of the last)")
     ap.add_argument("--case", default="default", choices=["default", "pe_err", "low_thr", "c3_sample", "c5_sample"],
                     help="the dataset of the in-process comparison")
+    ap.add_argument("--input", default="", help="an .npz of per-rank reads and the CPU oracle's results (with --k)")
+    ap.add_argument("--k", type=int, default=0, help="k of the --input comparison")
+    ap.add_argument("--fastx", default="", help="--input: each rank reads its part of this FASTQ file instead")
     a = ap.parse_args()
 
     def make_comm(ctx):
@@ -87,6 +236,9 @@ def main() -> int:
         with open(a.uid_file, "rb") as f:
             uid = f.read()
         return M.Comm.rccl(ctx, a.world, a.rank, uid)
+
+    if a.input:
+        return input_mode(a, make_comm)
 
     if a.config:
         import json
