@@ -1081,6 +1081,9 @@ bool msd_sort(mcaat_ctx *ctx, const uint64_t *ckeys, const uint32_t *ccnt, uint6
         launch_at(st, dim3((unsigned)ctx->n_cu * 5), dim3(kL3Waves * 64), k_msd3_wave, l2.p, off2.p, real, base, k, key,
                   mult, big.p, nbig.p, limit("sort.wave_limit", kWaveSort), knob(ctx, "sort.l3_counting", 1));
         uint64_t hb = read_counter(st, nbig.p);
+        // the stages' forward counts as statistics (tests/test_sort_occupancy.py holds them against
+        // the bucket histogram of its own reference)
+        ctx->kstats["msd3_listed"].launches += hb;
         if (hb) {
             DevBuf<uint32_t> big2(hb);
             DevBuf<unsigned long long> nbig2(1);
@@ -1099,6 +1102,7 @@ bool msd_sort(mcaat_ctx *ctx, const uint64_t *ckeys, const uint32_t *ccnt, uint6
                 launch_at(st, grid(hb, 8), dim3(128), k_msd3_count<128, kSmallMid>, l2.p, off2.p, real, base, k, big.p,
                           hb, key, mult, big1.p, nbig1.p, limit("sort.small_limit", kSmallMid));
                 hb = read_counter(st, nbig1.p);
+                ctx->kstats["msd3_small_fwd"].launches += hb;
                 HIP_OK(hipMemcpyAsync(big.p, big1.p, 4 * hb, hipMemcpyDeviceToDevice, st));
             }
             // mid (deep graphs: D / 2^22 above the wave limit): 256-thread workgroups, 24 KB of LDS, four
@@ -1109,10 +1113,14 @@ bool msd_sort(mcaat_ctx *ctx, const uint64_t *ckeys, const uint32_t *ccnt, uint6
                           key, mult, big2.p, nbig2.p, mid_limit);
             // block: the rare larger ones by one 1024-thread workgroup each
             const uint64_t hb2 = read_counter(st, nbig2.p);
+            ctx->kstats["msd3_mid_fwd"].launches += hb2;
             if (hb2)
                 launch_at(st, grid(hb2, 1), dim3(1024), k_msd3_block<1024, kBlockSort>, l2.p, off2.p, real, base, k,
                           big2.p, hb2, key, mult, nullptr, nullptr, too.p, limit("sort.block_limit", kBlockSort));
-            if (read_counter(st, too.p)) return false;
+            if (read_counter(st, too.p)) {
+                ctx->kstats["msd3_radix_fallback"].launches += 1;
+                return false;
+            }
         }
         HIP_OK(hipStreamSynchronize(st));
         return true;

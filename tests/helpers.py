@@ -75,6 +75,53 @@ def brute_neighbors(edges, k):
     return out, inc
 
 
+# ---- vectorised forms over code arrays (A=0 C=1 G=2 T=3), for read sets built edge by edge ----
+def pack_codes(flat, lens):
+    """pack_reads for reads given as one uint8 code stream and their lengths."""
+    flat = np.asarray(flat, dtype=np.uint64)
+    total = flat.size
+    nw = (total + 31) // 32
+    pad = np.zeros(nw * 32, dtype=np.uint64)
+    pad[:total] = flat
+    words = np.bitwise_or.reduce(pad.reshape(nw, 32) << (np.arange(32, dtype=np.uint64) * np.uint64(2)), axis=1)
+    offs = np.zeros(len(lens) + 1, dtype=np.uint64)
+    offs[1:] = np.cumsum(np.asarray(lens, dtype=np.uint64))
+    assert int(offs[-1]) == total
+    return words.astype(np.uint64), offs
+
+
+def pack_code_groups(groups):
+    """pack_codes for a list of 2-D code arrays (one read per row, equal lengths per array)."""
+    flat = np.concatenate([g.reshape(-1) for g in groups])
+    lens = np.concatenate([np.full(g.shape[0], g.shape[1], dtype=np.uint64) for g in groups])
+    return pack_codes(flat, lens)
+
+
+def boss_keys(codes, k):
+    """boss_key of every row of an (n, k+1) code array, as uint64."""
+    codes = np.asarray(codes)
+    assert codes.ndim == 2 and codes.shape[1] == k + 1
+    key = codes[:, k].astype(np.uint64)
+    for j in range(k):
+        key |= codes[:, j].astype(np.uint64) << np.uint64(2 * j + 2)
+    return key
+
+
+def edge_codes(keys, k):
+    """The (n, k+1) code array whose boss_keys are `keys`."""
+    keys = np.asarray(keys, dtype=np.uint64)
+    out = np.empty((keys.size, k + 1), dtype=np.uint8)
+    for j in range(k):
+        out[:, j] = (keys >> np.uint64(2 * j + 2)) & np.uint64(3)
+    out[:, k] = keys & np.uint64(3)
+    return out
+
+
+def rc_codes(codes):
+    """Reverse complement of every row."""
+    return (3 - np.asarray(codes)[:, ::-1]).astype(np.uint8)
+
+
 class HipBuffer:
     """A device buffer from the HIP runtime libmcaat_gpu.so itself links (libamdhip64), for tests
     that hand device pointers to the C ABI. (torch ships its own HIP runtime; two runtimes in one
