@@ -63,8 +63,14 @@ int mcaat_reads_from_host(mcaat_ctx *ctx, const uint64_t *packed, uint64_t n_wor
 /* Non-ACGT symbols split a read (k-mers spanning them are dropped). gzip via zlib, bzip2 via
  * libbz2 (opened at run time; concatenated members / streams read in sequence).
  * FASTQ inputs (4-line records) are parsed on the GPU in chunks (csrc/fastq_ingest.hip;
- * chunk size MCAAT_FASTQ_CHUNK bytes, default 256 MiB); FASTA (multi-line) on the host.
- * Blank lines are accepted only before the first and after the last record. */
+ * chunk size MCAAT_FASTQ_CHUNK bytes, default 256 MiB); there blank lines are accepted only
+ * before the first and after the last record. FASTA inputs (a '>' header line, then any number
+ * of sequence lines; empty lines are transparent, a run of ACGT that continues over a line
+ * break is one read) are parsed on the GPU too, by line, in the same chunks (knob fa.gpu).
+ * What neither parser takes is read again by the host kseq-style reader, with the same results:
+ * FASTA and FASTQ mixed, wrapped or gapped FASTQ, a FASTA sequence line that starts with '@' or
+ * '+' (FASTQ grammar to kseq), a record longer than the carry reserve (a quarter of the chunk,
+ * at least 4096 bytes). */
 int mcaat_reads_from_fastx(mcaat_ctx *ctx, const char *const *files, int n_files, mcaat_reads **out);
 /* (round 5) The next mcaat_reads_from_fastx on ctx runs node_counter's pass A for k (the
  * super-k-mer scatter of the k+1-mers) on each part of a host-packed FASTQ input while the
@@ -303,11 +309,14 @@ int mcaat_comm_barrier(mcaat_comm *c);
 int mcaat_comm_allgather_sizes(mcaat_comm *c, uint64_t bytes, uint64_t *sizes);
 int mcaat_comm_allgatherv(mcaat_comm *c, const void *send, uint64_t bytes, void *recv, const uint64_t *sizes);
 void mcaat_comm_free(mcaat_comm *c);
-/* Part `part` of n_parts of the FASTQ inputs (replaces BuildLib for one rank): each plain
- * file is cut at 4-line record starts near part/n_parts of its size, a .gz file goes whole
- * to part 0 (one inflate stream cannot be split). MCAAT_E_IO for inputs the GPU parser does
- * not take (FASTA, wrapped or gapped records): read them whole with mcaat_reads_from_fastx
- * on one rank instead. n_parts == 1 is mcaat_reads_from_fastx. */
+/* Part `part` of n_parts of the inputs, all FASTQ or all FASTA (replaces BuildLib for one
+ * rank): each plain file is cut near part/n_parts of its size, a FASTQ file at 4-line record
+ * starts, a FASTA file at the first line start at or after S*part/n_parts whose first byte is
+ * '>' (csrc/fasta_split.h; a part that holds no header is empty); a .gz / .bz2 file goes whole
+ * to part 0 (one inflate stream cannot be split). MCAAT_E_IO for inputs the GPU parsers do not
+ * take (FASTA and FASTQ mixed, wrapped or gapped FASTQ, FASTA with a sequence line that starts
+ * with '@' or '+' or a record above the carry reserve, FASTA with fa.gpu = 0): read them whole
+ * with mcaat_reads_from_fastx on one rank instead. n_parts == 1 is mcaat_reads_from_fastx. */
 int mcaat_reads_from_fastx_part(mcaat_ctx *ctx, const char *const *files, int n_files, int part, int n_parts,
                                 mcaat_reads **out);
 /* mapping-view records that came from input file `file` (they are in file order) */
@@ -404,6 +413,9 @@ void mcaat_reset_timing(mcaat_ctx *ctx);
  *                      start-candidate list (regrowth test knobs)
  *   fq.hostpack        0: FASTQ always through the GPU text parser (default 1: plain files of
  *                      upper-case ACGT 4-line records packed to 2 bits by host threads first)
+ *   fa.gpu             0: FASTA always through the host kseq-style reader, and never split over
+ *                      ranks (default 1: parsed on the GPU by line; kernel timers fa_parse,
+ *                      fa_lines, fa_emit). The user's fallback and the tests' A/B switch
  *   sdbg.adj_lds       0: adjacency by per-edge directory searches in global memory (the tests'
  *                      independent reference); 1 (default): group-aligned runs that own disjoint
  *                      in_info slot ranges, staged in LDS and written once. Any other value is

@@ -169,9 +169,10 @@ int sniff_format(const char *path) {
 }
 
 // Host reader with the reference's kseq semantics (klib kseq_read, as MEGAHIT buildlib and
-// kseq++ in reads.cpp read records): FASTA, and the FASTQ inputs the 4-line GPU parser hands
-// back (blank lines between records, wrapped sequence/quality lines, records longer than its
-// carry reserve). A record starts at the next '>' or '@'; its header line is skipped; sequence
+// kseq++ in reads.cpp read records): FASTA and FASTQ mixed, FASTA with the knob fa.gpu = 0, and
+// the inputs the GPU parsers hand back (FASTQ with blank lines between records or wrapped
+// sequence/quality lines, FASTA with a sequence line that starts with '@' or '+', records
+// longer than the carry reserve). A record starts at the next '>' or '@'; its header line is skipped; sequence
 // lines are concatenated (blank lines skipped, one trailing '\r' dropped) up to a line that
 // starts with '>', '@' or '+'; after '+' the rest of that line is skipped and quality lines are
 // read until they hold at least as many characters as the sequence (at least one line); any
@@ -488,8 +489,16 @@ int mcaat_reads_from_fastx(mcaat_ctx *ctx, const char *const *files, int n_files
                 } catch (const FormatError &) {
                     host_path();
                 }
+            } else if (n_fasta > 0 && n_fastq == 0 && knob(ctx, "fa.gpu", 1) != 0) {
+                // FASTA on the GPU, by line; inputs it does not take (a sequence line that starts
+                // with '@' or '+', records above its carry reserve) are read again on the host
+                try {
+                    ingest_fasta(ctx, files, n_files, r);
+                } catch (const FormatError &) {
+                    host_path();
+                }
             } else {
-                host_path();  // FASTA, FASTA + FASTQ, or only empty files
+                host_path();  // FASTA + FASTQ, only empty files, or FASTA with fa.gpu = 0
             }
         } catch (...) {
             delete r;
@@ -1108,7 +1117,7 @@ int mcaat_set_knob(mcaat_ctx *ctx, const char *name, int64_t value) {
         "fq.hostpack",     "nc.big_table", "cf.fused_init", "cf.dls_lanes", "dist.oriented",
         "sort.small_mid", "sort.small_limit", "cf.dls_host",
         "dist.desc",      "cf.compact",         "cf.fresh",   "nc.split_first", "nc.split_max", "cf.dls_budget", "nc.grow_early",
-        "nc.free_sync", "dist.shard_cf", "dist.ruler_mask", "dist.adj_chunk", "dist.dir_edges", "nc.ahead", "dist.adj_ranges", "dist.win_ranges", "cf.dls_lds", "cf.dls_lds_cap", "dist.segs_at_one", "nc.a_mini", "nc.a_adapt", "nc.a_stats", "dist.bfs_sync", "cf.compact_pct", "dist.bfs_block", "dist.bfs_frontier", "dist.res_fixed", "dist.res_batch", "dist.res_block_mb", "dist.walk_block", "dist.walk_batch", "dist.grid_blocks", "dist.preagg"};
+        "nc.free_sync", "dist.shard_cf", "dist.ruler_mask", "dist.adj_chunk", "dist.dir_edges", "nc.ahead", "dist.adj_ranges", "dist.win_ranges", "cf.dls_lds", "cf.dls_lds_cap", "dist.segs_at_one", "nc.a_mini", "nc.a_adapt", "nc.a_stats", "dist.bfs_sync", "cf.compact_pct", "dist.bfs_block", "dist.bfs_frontier", "dist.res_fixed", "dist.res_batch", "dist.res_block_mb", "dist.walk_block", "dist.walk_batch", "dist.grid_blocks", "dist.preagg", "fa.gpu"};
     return guarded([&] {
         require(ctx && name, "null argument");
         bool ok = false;
@@ -1248,9 +1257,18 @@ int mcaat_reads_from_fastx_part(mcaat_ctx *ctx, const char *const *files, int n_
         require(ctx && out && files && n_files > 0, "null argument");
         mcaat::bind(ctx);
         std::vector<std::pair<uint64_t, uint64_t>> ranges;
+        // all FASTQ or all FASTA (empty files go with either); a file is cut at record starts
+        int n_fastq = 0, n_fasta = 0;
         for (int i = 0; i < n_files; ++i) {
             const int c = sniff_format(files[i]);
-            if (c == '>') throw Error(MCAAT_E_IO, std::string("FASTA inputs are not split over ranks: ") + files[i]);
+            n_fastq += c == '@';
+            n_fasta += c == '>';
+        }
+        if (n_fasta > 0 && n_fastq > 0) throw Error(MCAAT_E_IO, "FASTA and FASTQ inputs mixed are not split over ranks");
+        if (n_fasta > 0 && knob(ctx, "fa.gpu", 1) == 0)
+            throw Error(MCAAT_E_IO, "FASTA inputs are not split over ranks with fa.gpu = 0");
+        const auto record_start = n_fasta > 0 ? fasta_record_start : fastq_record_start;
+        for (int i = 0; i < n_files; ++i) {
             if (is_compressed_file(files[i])) {
                 // one compressed stream cannot be split: part 0 reads the whole file
                 ranges.push_back(part == 0 ? std::make_pair(0ULL, ~0ULL) : std::make_pair(0ULL, 0ULL));
@@ -1259,15 +1277,16 @@ int mcaat_reads_from_fastx_part(mcaat_ctx *ctx, const char *const *files, int n_
             struct stat st;
             if (stat(files[i], &st) != 0) throw Error(MCAAT_E_IO, std::string("cannot stat ") + files[i]);
             const uint64_t S = (uint64_t)st.st_size;
-            const uint64_t b = fastq_record_start(files[i], (uint64_t)((unsigned __int128)S * part / n_parts));
+            const uint64_t b = record_start(files[i], (uint64_t)((unsigned __int128)S * part / n_parts));
             const uint64_t e = part + 1 == n_parts
                                    ? S
-                                   : fastq_record_start(files[i], (uint64_t)((unsigned __int128)S * (part + 1) / n_parts));
+                                   : record_start(files[i], (uint64_t)((unsigned __int128)S * (part + 1) / n_parts));
             ranges.push_back({b, std::max(b, e)});
         }
         auto *r = new mcaat_reads;
         try {
-            ingest_fastq(ctx, files, n_files, r, &ranges);
+            if (n_fasta > 0) ingest_fasta(ctx, files, n_files, r, &ranges);
+            else ingest_fastq(ctx, files, n_files, r, &ranges);
         } catch (const FormatError &e) {
             delete r;
             throw Error(MCAAT_E_IO, std::string("input not split over ranks (read it whole): ") + e.what());

@@ -22,8 +22,27 @@
 //
 // Bytes per chunk byte (roofline, HBM): ~2.5 B read (two newline passes + the record
 // passes) + 0.25 B per sequence byte written per view. The ingest is PCIe/host-read bound
-// (text crosses PCIe once); the parse runs at HBM speed. FASTA (multi-line records) stays
-// on the host parser in capi.hip.
+// (text crosses PCIe once); the parse runs at HBM speed.
+//
+// FASTA (ingest_fasta) shares the source, the chunks, the copy stream and the newline passes
+// (ChunkIo), and deals its work by line, not by record: a wrapped contig is one record of
+// tens of thousands of lines.
+//
+//  3'. k_fa_lines    one lane per line: class (header '>' / sequence / empty), trimmed length,
+//                    ACGT count, run starts, whether the first and the last symbol are ACGT;
+//                    a sequence line that starts with '@' or '+' declines the input (kseq
+//                    reads FASTQ grammar there: the host reader takes it).
+//      scans         headers before a line (its record), the nearest non-empty line before it
+//                    (max-scan), and after k_fa_link base, read and symbol offsets.
+//      k_fa_link     a run open at a line's end continues in the record's next non-empty line
+//                    (one read, also across empty lines; never across a header).
+//  4'. k_fa_emit     one lane per line: both views packed as above; a record of a later file
+//                    is reversed and complemented over the whole concatenated record, so a
+//                    line writes backwards from its mirrored place in the record.
+//
+// A chunk is consumed up to the start of its last header line. Records above the carry
+// reserve, FASTA mixed with FASTQ and kseq's FASTQ grammar inside a FASTA file stay on the
+// host parser in capi.hip. A very long unwrapped line is parsed by one lane (correct, slow).
 #include <hipcub/hipcub.hpp>
 #include <zlib.h>
 
@@ -39,6 +58,7 @@
 
 #include <thread>
 
+#include "fasta_split.h"
 #include "internal.h"
 
 namespace mcaat {
@@ -257,6 +277,141 @@ __global__ void k_fq_emit(const uint8_t *buf, uint32_t n_rec, const uint32_t *sb
     }
 }
 
+// ---- FASTA: work dealt by line (a wrapped contig is one record of many thousand lines) ----
+
+enum : uint32_t { kLHeader = 1, kLFirst = 2, kLLast = 4, kLCont = 8 };  // per-line flags
+
+// per line: class (header / sequence / empty), trimmed length, ACGT count, run starts, whether
+// its first and last symbols are ACGT. key[i] orders the non-empty lines for the max-scan that
+// hands every line its nearest non-empty predecessor: (i + 1) << 1 | last-symbol-is-ACGT, 0 for
+// an empty line. meta[0]: flags; meta[1], meta[2]: index + 1 and start of the last header line.
+__global__ void k_fa_lines(const uint8_t *buf, const uint32_t *nl, uint32_t n_lines, uint32_t *len, uint32_t *nbase,
+                           uint32_t *nrun, uint32_t *lflag, uint32_t *hflag, uint32_t *key, uint32_t *meta) {
+    const uint32_t stride = gridDim.x * blockDim.x;
+    uint32_t fl = 0, h_idx = 0, h_pos = 0;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_lines; i += stride) {
+        const uint32_t s = i ? nl[i - 1] + 1 : 0;
+        uint32_t e = nl[i];
+        if (e > s && buf[e - 1] == '\r') --e;
+        const uint8_t c0 = buf[s];
+        if (c0 == '>') {  // skipped whole: '>', '@' and '+' inside it mean nothing
+            len[i] = nbase[i] = nrun[i] = 0;
+            lflag[i] = kLHeader;
+            hflag[i] = 1;
+            key[i] = (i + 1) << 1;
+            h_idx = i + 1;
+            h_pos = s;
+            continue;
+        }
+        // kseq starts a FASTQ-style record at '@' and a quality block at '+': not pure FASTA. A
+        // chunk begins at a header line (line 0), or the file's first byte was no '>'.
+        if (c0 == '@' || c0 == '+' || i == 0) fl |= kBadHeader;
+        uint32_t bases = 0, runs = 0;
+        bool in = false, first = false;
+        Fwd rd(buf, s);
+        for (uint32_t j = s; j < e; ++j) {
+            const uint8_t c = rd.next();
+            if (count_code(c) >= 0) {
+                ++bases;
+                runs += !in;
+                in = true;
+                first |= j == s;
+            } else {
+                in = false;
+            }
+            if (c != 'A' && c != 'C' && c != 'G' && c != 'T') fl |= kDiffer;
+        }
+        len[i] = e - s;
+        nbase[i] = bases;
+        nrun[i] = runs;
+        lflag[i] = (first ? kLFirst : 0) | (in ? kLLast : 0);
+        hflag[i] = 0;
+        key[i] = e > s ? ((i + 1) << 1) | (in ? 1u : 0u) : 0u;
+    }
+    if (fl) atomicOr(meta, fl);
+    if (h_idx) {
+        atomicMax(meta + 1, h_idx);
+        atomicMax(meta + 2, h_pos);
+    }
+}
+
+// A run that is open at the end of a record's line continues in the record's next non-empty
+// line when that begins with an ACGT symbol: it is one read, so the continuing line has one run
+// start less. Never across a header (a header's key has the ACGT bit clear). hdr[r] is the line
+// of record r's header, hdr[n_rec] the line count.
+__global__ void k_fa_link(uint32_t n_lines, const uint32_t *prev, const uint32_t *recx, uint32_t *nrun, uint32_t *lflag,
+                          uint32_t *hdr) {
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i <= n_lines; i += stride) {
+        if (i == n_lines) {
+            hdr[recx[i]] = i;
+            continue;
+        }
+        const uint32_t lf = lflag[i];
+        if (lf & kLHeader) {
+            hdr[recx[i]] = i;
+        } else if ((lf & kLFirst) && (prev[i] & 1)) {
+            nrun[i] -= 1;
+            lflag[i] = lf | kLCont;
+        }
+    }
+}
+
+// one lane per line. A sequence line packs its symbols into both views: the counting view at
+// its base offset (a read's start offset is written where its run starts: offsets[i] is both
+// the end of read i-1 and the start of read i; the host writes the last entry), the mapping
+// view at its offset in the record, from the record's far end backwards when the file's records
+// are reversed and complemented. A header line writes its record's end offset.
+__global__ void k_fa_emit(const uint8_t *buf, const uint32_t *nl, uint32_t n_lines, const uint32_t *len,
+                          const uint32_t *lflag, const uint32_t *recx, const uint32_t *hdr, const uint32_t *boff,
+                          const uint32_t *roff, const uint32_t *qoff, uint64_t g_base, uint64_t g_read, uint64_t g_qbase,
+                          uint64_t g_rec, int reverse, uint64_t *packed, uint64_t *offsets, uint64_t *qpacked,
+                          uint64_t *qoffsets, uint32_t *meta) {
+    const uint32_t stride = gridDim.x * blockDim.x;
+    uint32_t fl = 0;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_lines; i += stride) {
+        const uint32_t lf = lflag[i];
+        if (lf & kLHeader) {
+            const uint32_t r = recx[i], next = hdr[r + 1];
+            if (roff[next] - roff[i] != 1) fl |= kDiffer;  // not exactly one run
+            qoffsets[1 + g_rec + r] = g_qbase + qoff[next];
+            continue;
+        }
+        const uint32_t L = len[i];
+        if (!L) continue;
+        const uint32_t sb = nl[i - 1] + 1;  // line 0 is a header
+        PackWriter pw(packed, g_base + boff[i]);
+        uint64_t ri = g_read + roff[i];
+        bool in = (lf & kLCont) != 0;
+        Fwd rd(buf, sb);
+        for (uint32_t j = 0; j < L; ++j) {
+            const int b = count_code(rd.next());
+            if (b >= 0) {
+                if (!in) offsets[ri++] = pw.pos;
+                in = true;
+                pw.put((uint32_t)b);
+            } else {
+                in = false;
+            }
+        }
+        pw.finish();
+        if (!reverse) {
+            PackWriter qw(qpacked, g_qbase + qoff[i]);
+            Fwd rq(buf, sb);
+            for (uint32_t j = 0; j < L; ++j) qw.put(map_code(rq.next()));
+            qw.finish();
+        } else {
+            const uint32_t r = recx[i] - 1;  // headers before this line, less one
+            const uint32_t r0 = qoff[hdr[r]], r1 = qoff[hdr[r + 1]];
+            PackWriter qw(qpacked, g_qbase + r1 - (qoff[i] - r0) - L);
+            Bwd rq(buf, sb + L - 1);
+            for (uint32_t j = 0; j < L; ++j) qw.put(map_code_rc(rq.next()));
+            qw.finish();
+        }
+    }
+    if (fl) atomicOr(meta, fl);
+}
+
 __global__ void k_fq_fixed_len(const uint64_t *off, uint64_t n, uint64_t L, uint32_t *bad) {
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     bool b = false;
@@ -359,48 +514,54 @@ size_t fastq_chunk_bytes() {
     return size_t(256) << 20;
 }
 
-// All inputs are FASTQ (checked by the caller). Files are concatenated; records of files
-// after the first are reversed and complemented in the mapping view (paired-end R2).
-void ingest_fastq(mcaat_ctx *ctx, const char *const *files, int n_files, mcaat_reads *r,
-                  const std::vector<std::pair<uint64_t, uint64_t>> *ranges) {
-    // plain files of well-formed upper-case ACGT records: packed by host threads (PCIe carries
-    // 2 bits per base); any other input falls through to the text parser below
-    if (fastq_hostpack(ctx, files, n_files, ranges, r)) return;
-    const size_t CH = fastq_chunk_bytes();
-    const size_t R = std::max<size_t>(CH / 4, 4096);  // carry reserve: the longest record that fits
-    const size_t cap = R + CH + 2 * kSeg;
+namespace {
 
-    uint64_t est = 0;  // stream capacity estimate from the input sizes (grown on demand)
-    for (int i = 0; i < n_files; ++i) {
-        struct stat st;
-        const std::string path(files[i]);
-        const bool gz = (path.size() > 3 && path.compare(path.size() - 3, 3, ".gz") == 0) ||
-                        (path.size() > 4 && path.compare(path.size() - 4, 4, ".bz2") == 0);
-        if (stat(files[i], &st) == 0) {
-            uint64_t sz = (uint64_t)st.st_size;
-            if (ranges) sz = std::min(sz, (*ranges)[i].second) - std::min(sz, (*ranges)[i].first);
-            est += sz * (gz ? 4 : 1);
-        }
-    }
-    DevBuf<uint64_t> packed(est / 64 + 1024), offsets(est / 256 + 1024);
-    DevBuf<uint64_t> qpacked(est / 64 + 1024), qoffsets(est / 256 + 1024);
-    for (auto *b : {&packed, &offsets, &qpacked, &qoffsets}) HIP_OK(hipMemsetAsync(b->p, 0, b->bytes(), ctx->stream));
+using Ranges = std::vector<std::pair<uint64_t, uint64_t>>;
+
+// The two views of the read library as growing device streams, and what they hold so far.
+struct Library {
+    DevBuf<uint64_t> packed, offsets, qpacked, qoffsets;
     uint64_t n_bases = 0, n_reads = 0, q_bases = 0, n_rec = 0;
-    uint32_t flags_all = 0;
-
-    if (ctx->pinned_bytes < cap) {
-        for (auto *&p : ctx->pinned) {
-            if (p) (void)hipHostFree(p);
-            p = nullptr;
+    std::vector<uint64_t> file_records;
+    // stream capacity estimate from the input sizes (grown on demand)
+    Library(mcaat_ctx *ctx, const char *const *files, int n_files, const Ranges *ranges) {
+        uint64_t est = 0;
+        for (int i = 0; i < n_files; ++i) {
+            struct stat st;
+            const std::string path(files[i]);
+            const bool gz = (path.size() > 3 && path.compare(path.size() - 3, 3, ".gz") == 0) ||
+                            (path.size() > 4 && path.compare(path.size() - 4, 4, ".bz2") == 0);
+            if (stat(files[i], &st) == 0) {
+                uint64_t sz = (uint64_t)st.st_size;
+                if (ranges) sz = std::min(sz, (*ranges)[i].second) - std::min(sz, (*ranges)[i].first);
+                est += sz * (gz ? 4 : 1);
+            }
         }
-        ctx->pinned_bytes = 0;
-        for (auto *&p : ctx->pinned) HIP_OK(hipHostMalloc((void **)&p, cap, hipHostMallocDefault));
-        ctx->pinned_bytes = cap;
+        packed.alloc(est / 64 + 1024);
+        offsets.alloc(est / 256 + 1024);
+        qpacked.alloc(est / 64 + 1024);
+        qoffsets.alloc(est / 256 + 1024);
+        for (auto *b : {&packed, &offsets, &qpacked, &qoffsets}) HIP_OK(hipMemsetAsync(b->p, 0, b->bytes(), ctx->stream));
     }
-    uint8_t *hb[2] = {ctx->pinned[0], ctx->pinned[1]};
+    // room for cb bases in cr reads and cq symbols in nrec records more
+    void reserve(mcaat_ctx *ctx, uint32_t cb, uint32_t cr, uint32_t cq, uint32_t nrec) {
+        grow(ctx, packed, (n_bases + 31) / 32 + 1, (n_bases + cb + 31) / 32 + 17);
+        grow(ctx, offsets, n_reads + 1, n_reads + cr + 2);
+        grow(ctx, qpacked, (q_bases + 31) / 32 + 1, (q_bases + cq + 31) / 32 + 17);
+        grow(ctx, qoffsets, n_rec + 1, n_rec + nrec + 2);
+    }
+};
+
+// The host side of a chunked text ingest, shared by the FASTQ and the FASTA parser: two pinned
+// chunks that a reader task fills, their device copies uploaded on a copy stream while the
+// previous chunk is parsed, the newline passes, and the loop over files and chunks.
+struct ChunkIo {
+    mcaat_ctx *ctx;
+    const size_t CH;   // new bytes per chunk
+    const size_t R;    // carry reserve: the longest record that fits
+    const size_t cap;  // bytes of a chunk buffer
+    uint8_t *hb[2];
     DevBuf<uint8_t> dbufs[2];
-    dbufs[0].alloc(cap);
-    dbufs[1].alloc(cap);
     struct CopyStream {  // uploads overlap the parse of the previous chunk
         hipStream_t s = nullptr;
         hipEvent_t ev[2] = {nullptr, nullptr};    // upload into dbufs[x] complete
@@ -419,31 +580,54 @@ void ingest_fastq(mcaat_ctx *ctx, const char *const *files, int n_files, mcaat_r
             if (s) (void)hipStreamDestroy(s);
         }
     } cs;
-    for (auto &e : cs.done) HIP_OK(hipEventRecord(e, ctx->stream));
-    hipEvent_t *up_ev = cs.ev;
-    const uint64_t max_seg = cap / kSeg + 1;
-    DevBuf<uint32_t> cnt(max_seg + 1), first(max_seg + 1), nl(cap + 16);  // every byte may be a newline
-    DevBuf<uint32_t> sbeg, slen, nbase, nrun, boff, roff, qoff;
-    DevBuf<uint32_t> meta(8);
-    DevBuf<uint8_t> tmp(1 << 20);
-    uint32_t *hmeta = nullptr;
-    HIP_OK(hipHostMalloc((void **)&hmeta, 64, hipHostMallocDefault));
-    struct MetaFree {
-        uint32_t *p;
-        ~MetaFree() { (void)hipHostFree(p); }
-    } meta_free{hmeta};
+    DevBuf<uint32_t> cnt, first, nl;
+    DevBuf<uint32_t> meta;
+    DevBuf<uint8_t> tmp;
+    uint32_t *hmeta = nullptr;  // pinned words for the counters read back per chunk
 
-    // chunk x: host bytes [start, start+total) of hb[x] (carry + new data, blank lines trimmed
-    // at the file's ends) uploaded on the copy stream into dbufs[x]; up_ev[x] marks completion
-    auto prepare = [&](int x, size_t carry_x, size_t n_x, bool eof_x, bool first_x, uint8_t *&start_x,
-                       size_t &total_x) {
+    explicit ChunkIo(mcaat_ctx *c)
+        : ctx(c), CH(fastq_chunk_bytes()), R(std::max<size_t>(CH / 4, 4096)), cap(R + CH + 2 * kSeg) {
+        if (ctx->pinned_bytes < cap) {
+            for (auto *&p : ctx->pinned) {
+                if (p) (void)hipHostFree(p);
+                p = nullptr;
+            }
+            ctx->pinned_bytes = 0;
+            for (auto *&p : ctx->pinned) HIP_OK(hipHostMalloc((void **)&p, cap, hipHostMallocDefault));
+            ctx->pinned_bytes = cap;
+        }
+        hb[0] = ctx->pinned[0];
+        hb[1] = ctx->pinned[1];
+        dbufs[0].alloc(cap);
+        dbufs[1].alloc(cap);
+        for (auto &e : cs.done) HIP_OK(hipEventRecord(e, ctx->stream));
+        const uint64_t max_seg = cap / kSeg + 1;
+        cnt.alloc(max_seg + 1);
+        first.alloc(max_seg + 1);
+        nl.alloc(cap + 16);  // every byte may be a newline
+        meta.alloc(8);
+        tmp.alloc(1 << 20);
+        HIP_OK(hipHostMalloc((void **)&hmeta, 64, hipHostMallocDefault));
+    }
+    ~ChunkIo() {
+        if (hmeta) (void)hipHostFree(hmeta);
+    }
+    ChunkIo(const ChunkIo &) = delete;
+    ChunkIo &operator=(const ChunkIo &) = delete;
+
+    // chunk x: host bytes [start, start+total) of hb[x] (carry + new data; blank bytes trimmed
+    // at the file's start and, with trim_tail, at its end; a last line without its newline gets
+    // one) uploaded on the copy stream into dbufs[x]; cs.ev[x] marks completion
+    void prepare(int x, size_t carry_x, size_t n_x, bool eof_x, bool first_x, bool trim_tail, uint8_t *&start_x,
+                 size_t &total_x) {
         start_x = hb[x] + R - carry_x;
         total_x = carry_x + n_x;
         if (first_x)  // leading blank lines
             while (total_x && is_space(*start_x)) ++start_x, --total_x;
-        if (eof_x) {  // trailing blank lines; the last line gets its newline
-            while (total_x && is_space(start_x[total_x - 1])) --total_x;
-            if (total_x) start_x[total_x++] = '\n';
+        if (eof_x) {
+            if (trim_tail)
+                while (total_x && is_space(start_x[total_x - 1])) --total_x;
+            if (total_x && (trim_tail || start_x[total_x - 1] != '\n')) start_x[total_x++] = '\n';
         }
         if (total_x) {
             const size_t padded = (total_x + kSeg - 1) / kSeg * kSeg + kSeg;
@@ -451,147 +635,272 @@ void ingest_fastq(mcaat_ctx *ctx, const char *const *files, int n_files, mcaat_r
             HIP_OK(hipStreamWaitEvent(cs.s, cs.done[x], 0));
             HIP_OK(hipMemcpyAsync(dbufs[x].p, start_x, total_x, hipMemcpyHostToDevice, cs.s));
             HIP_OK(hipMemsetAsync(dbufs[x].p + total_x, 0, padded - total_x, cs.s));
-            HIP_OK(hipEventRecord(up_ev[x], cs.s));
-        }
-    };
-    std::vector<uint64_t> file_records;
-    for (int fi = 0; fi < n_files; ++fi) {
-        const uint64_t rec_before = n_rec;
-        struct FileDone {  // records of this file, however the loop below is left
-            std::vector<uint64_t> &v;
-            const uint64_t &n, before;
-            ~FileDone() { v.push_back(n - before); }
-        } file_done{file_records, n_rec, rec_before};
-        if (ranges && (*ranges)[fi].first >= (*ranges)[fi].second) continue;  // no part of this file
-        Source src(files[fi], ranges ? (*ranges)[fi].first : 0, ranges ? (*ranges)[fi].second : ~0ULL);
-        int cur = 0;
-        size_t n = src.read(hb[cur] + R, CH);
-        bool eof = n < CH;
-        uint8_t *start = nullptr;
-        size_t total = 0;
-        prepare(cur, 0, n, eof, true, start, total);
-        std::future<size_t> next;
-        if (!eof) {
-            uint8_t *dst = hb[cur ^ 1] + R;
-            next = std::async(std::launch::async, [&src, dst, CH] { return src.read(dst, CH); });
-        }
-        for (;;) {
-            // ---- newline passes (after this chunk's upload)
-            const uint32_t nseg = (uint32_t)((total + kSeg - 1) / kSeg);
-            if (total) {
-                HIP_OK(hipStreamWaitEvent(ctx->stream, up_ev[cur], 0));
-                KernelTimer kt(ctx, "fq_parse", 2.0 * (double)total);
-                HIP_OK(hipMemsetAsync(cnt.p + nseg, 0, 4, ctx->stream));
-                launch_at(ctx->stream, dim3(grid_for(nseg, kBlock)), dim3(kBlock), k_fq_nlcount, dbufs[cur].p, nseg, cnt.p);
-                scan_u32(ctx, cnt.p, first.p, (uint64_t)nseg + 1, tmp);
-                launch_at(ctx->stream, dim3(grid_for(nseg, kBlock)), dim3(kBlock), k_fq_nlpos, dbufs[cur].p, nseg, first.p,
-                          nl.p);
-                HIP_OK(hipMemcpyAsync(hmeta, first.p + nseg, 4, hipMemcpyDeviceToHost, ctx->stream));
-                HIP_OK(hipStreamSynchronize(ctx->stream));
-                kt.stop();
-            }
-            const uint32_t NL = total ? hmeta[0] : 0;
-            const uint32_t nrec = NL / 4;
-            if (eof && NL % 4)
-                throw FormatError(std::string("not 4-line FASTQ (truncated record, blank or wrapped line): ") + files[fi]);
-            size_t consumed = 0;
-            if (nrec) {
-                HIP_OK(hipMemcpyAsync(hmeta, nl.p + 4 * (uint64_t)nrec - 1, 4, hipMemcpyDeviceToHost, ctx->stream));
-                HIP_OK(hipStreamSynchronize(ctx->stream));
-                consumed = (size_t)hmeta[0] + 1;
-            }
-            if (!eof && total - consumed > R)
-                throw FormatError(std::string("FASTQ record longer than the chunk reserve (") + std::to_string(R) +
-                                  " bytes): " + files[fi]);
-            // ---- the next chunk: its carry is known now, so it uploads while this chunk's
-            // records are parsed; this chunk's host buffer is free again for the reader
-            const bool have_next = !eof;
-            uint8_t *nstart = nullptr;
-            size_t ntotal = 0;
-            bool neof = true;
-            if (have_next) {
-                const size_t nn = next.get();
-                neof = nn < CH;
-                const size_t ncarry = total - consumed;
-                memcpy(hb[cur ^ 1] + R - ncarry, start + consumed, ncarry);
-                prepare(cur ^ 1, ncarry, nn, neof, false, nstart, ntotal);
-                if (!neof) {
-                    uint8_t *dst = hb[cur] + R;
-                    next = std::async(std::launch::async, [&src, dst, CH] { return src.read(dst, CH); });
-                }
-            }
-            // ---- records
-            if (nrec) {
-                KernelTimer kt(ctx, "fq_records", (double)consumed + 16.0 * nrec);
-                if (sbeg.n < (uint64_t)nrec + 1) {
-                    const uint64_t m = std::max<uint64_t>((uint64_t)nrec + 1, cap / 64);
-                    for (auto *b : {&sbeg, &slen, &nbase, &nrun, &boff, &roff, &qoff}) b->alloc(m);
-                }
-                HIP_OK(hipMemsetAsync(meta.p, 0, 4, ctx->stream));
-                for (auto *b : {&nbase, &nrun, &slen}) HIP_OK(hipMemsetAsync(b->p + nrec, 0, 4, ctx->stream));
-                launch_at(ctx->stream, dim3(grid_for(nrec, kBlock)), dim3(kBlock), k_fq_records, dbufs[cur].p, nl.p, nrec,
-                          sbeg.p, slen.p, nbase.p, nrun.p, meta.p);
-                scan_u32(ctx, nbase.p, boff.p, (uint64_t)nrec + 1, tmp);
-                scan_u32(ctx, nrun.p, roff.p, (uint64_t)nrec + 1, tmp);
-                scan_u32(ctx, slen.p, qoff.p, (uint64_t)nrec + 1, tmp);
-                HIP_OK(hipMemcpyAsync(hmeta + 0, boff.p + nrec, 4, hipMemcpyDeviceToHost, ctx->stream));
-                HIP_OK(hipMemcpyAsync(hmeta + 1, roff.p + nrec, 4, hipMemcpyDeviceToHost, ctx->stream));
-                HIP_OK(hipMemcpyAsync(hmeta + 2, qoff.p + nrec, 4, hipMemcpyDeviceToHost, ctx->stream));
-                HIP_OK(hipMemcpyAsync(hmeta + 3, meta.p, 4, hipMemcpyDeviceToHost, ctx->stream));
-                HIP_OK(hipStreamSynchronize(ctx->stream));
-                kt.stop();
-                const uint32_t cb = hmeta[0], cr = hmeta[1], cq = hmeta[2], fl = hmeta[3];
-                if (fl & kBadHeader) throw FormatError(std::string("not 4-line FASTQ (header or '+' line): ") + files[fi]);
-                flags_all |= fl;
-                if (fi > 0) flags_all |= kDiffer;  // second file: reverse-complemented records
-                grow(ctx, packed, (n_bases + 31) / 32 + 1, (n_bases + cb + 31) / 32 + 17);
-                grow(ctx, offsets, n_reads + 1, n_reads + cr + 2);
-                grow(ctx, qpacked, (q_bases + 31) / 32 + 1, (q_bases + cq + 31) / 32 + 17);
-                grow(ctx, qoffsets, n_rec + 1, n_rec + nrec + 2);
-                KernelTimer ke(ctx, "fq_emit", (double)consumed + 0.5 * (double)(cb + cq) + 8.0 * (cr + nrec));
-                launch_at(ctx->stream, dim3(grid_for(nrec, kBlock)), dim3(kBlock), k_fq_emit, dbufs[cur].p, nrec, sbeg.p,
-                          slen.p, boff.p, roff.p, qoff.p, n_bases, n_reads, q_bases, n_rec, fi > 0 ? 1 : 0, packed.p,
-                          offsets.p, qpacked.p, qoffsets.p);
-                ke.stop();
-                n_bases += cb;
-                n_reads += cr;
-                q_bases += cq;
-                n_rec += nrec;
-            }
-            HIP_OK(hipEventRecord(cs.done[cur], ctx->stream));
-            if (!have_next) break;
-            cur ^= 1;
-            start = nstart;
-            total = ntotal;
-            eof = neof;
+            HIP_OK(hipEventRecord(cs.ev[x], cs.s));
         }
     }
-    HIP_OK(hipStreamSynchronize(ctx->stream));
 
-    r->ctx = ctx;
-    r->n_reads = n_reads;
-    r->n_bases = n_bases;
-    r->n_words = (n_bases + 31) / 32;
-    r->fixed_len = 0;
-    if (n_reads > 0) {
-        uint64_t L = 0;
-        HIP_OK(hipMemcpy(&L, offsets.p + 1, 8, hipMemcpyDeviceToHost));
-        HIP_OK(hipMemsetAsync(meta.p, 0, 4, ctx->stream));
-        launch_at(ctx->stream, dim3(grid_for(n_reads + 1, kBlock)), dim3(kBlock), k_fq_fixed_len, offsets.p, n_reads, L,
-                  meta.p);
-        HIP_OK(hipMemcpyAsync(hmeta, meta.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+    // the newline passes over chunk x once its upload is complete: nl[] holds the position of
+    // every '\n'; their number is returned
+    uint32_t newlines(int x, size_t total, const char *timer) {
+        if (!total) return 0;
+        const uint32_t nseg = (uint32_t)((total + kSeg - 1) / kSeg);
+        HIP_OK(hipStreamWaitEvent(ctx->stream, cs.ev[x], 0));
+        KernelTimer kt(ctx, timer, 2.0 * (double)total);
+        HIP_OK(hipMemsetAsync(cnt.p + nseg, 0, 4, ctx->stream));
+        launch_at(ctx->stream, dim3(grid_for(nseg, kBlock)), dim3(kBlock), k_fq_nlcount, dbufs[x].p, nseg, cnt.p);
+        scan_u32(ctx, cnt.p, first.p, (uint64_t)nseg + 1, tmp);
+        launch_at(ctx->stream, dim3(grid_for(nseg, kBlock)), dim3(kBlock), k_fq_nlpos, dbufs[x].p, nseg, first.p, nl.p);
+        HIP_OK(hipMemcpyAsync(hmeta, first.p + nseg, 4, hipMemcpyDeviceToHost, ctx->stream));
         HIP_OK(hipStreamSynchronize(ctx->stream));
-        if (!hmeta[0] && L > 0) r->fixed_len = L;
+        kt.stop();
+        return hmeta[0];
     }
-    r->packed = std::move(packed);
-    r->offsets = std::move(offsets);
-    r->n_records = n_rec;
-    r->file_records = file_records;
-    r->has_records = (flags_all & kDiffer) != 0;
-    if (r->has_records) {
-        r->rec_packed = std::move(qpacked);
-        r->rec_offsets = std::move(qoffsets);
+
+    // Every file's chunks in turn. consume(fi, x, total, NL, eof) says how many bytes of chunk x
+    // (NL whole lines in `total` bytes) hold whole records; the rest is carried into the next
+    // chunk, which uploads while parse(fi, x, consumed) packs this one. file_records gets one
+    // entry per file: the growth of n_rec while that file was read.
+    template <class Consume, class Parse>
+    void run(const char *what, const char *nl_timer, bool trim_tail, const char *const *files, int n_files,
+             const Ranges *ranges, const uint64_t &n_rec, std::vector<uint64_t> &file_records, Consume consume,
+             Parse parse) {
+        const size_t chunk = CH;
+        for (int fi = 0; fi < n_files; ++fi) {
+            const uint64_t rec_before = n_rec;
+            struct FileDone {  // records of this file, however the loop below is left
+                std::vector<uint64_t> &v;
+                const uint64_t &n, before;
+                ~FileDone() { v.push_back(n - before); }
+            } file_done{file_records, n_rec, rec_before};
+            if (ranges && (*ranges)[fi].first >= (*ranges)[fi].second) continue;  // no part of this file
+            Source src(files[fi], ranges ? (*ranges)[fi].first : 0, ranges ? (*ranges)[fi].second : ~0ULL);
+            int cur = 0;
+            size_t n = src.read(hb[cur] + R, chunk);
+            bool eof = n < chunk;
+            uint8_t *start = nullptr;
+            size_t total = 0;
+            prepare(cur, 0, n, eof, true, trim_tail, start, total);
+            std::future<size_t> next;
+            if (!eof) {
+                uint8_t *dst = hb[cur ^ 1] + R;
+                next = std::async(std::launch::async, [&src, dst, chunk] { return src.read(dst, chunk); });
+            }
+            for (;;) {
+                const uint32_t NL = newlines(cur, total, nl_timer);
+                const size_t consumed = consume(fi, cur, total, NL, eof);
+                if (!eof && total - consumed > R)
+                    throw FormatError(std::string(what) + " record longer than the chunk reserve (" + std::to_string(R) +
+                                      " bytes): " + files[fi]);
+                // ---- the next chunk: its carry is known now, so it uploads while this chunk's
+                // records are parsed; this chunk's host buffer is free again for the reader
+                const bool have_next = !eof;
+                uint8_t *nstart = nullptr;
+                size_t ntotal = 0;
+                bool neof = true;
+                if (have_next) {
+                    const size_t nn = next.get();
+                    neof = nn < chunk;
+                    const size_t ncarry = total - consumed;
+                    memcpy(hb[cur ^ 1] + R - ncarry, start + consumed, ncarry);
+                    prepare(cur ^ 1, ncarry, nn, neof, false, trim_tail, nstart, ntotal);
+                    if (!neof) {
+                        uint8_t *dst = hb[cur] + R;
+                        next = std::async(std::launch::async, [&src, dst, chunk] { return src.read(dst, chunk); });
+                    }
+                }
+                parse(fi, cur, consumed);
+                HIP_OK(hipEventRecord(cs.done[cur], ctx->stream));
+                if (!have_next) break;
+                cur ^= 1;
+                start = nstart;
+                total = ntotal;
+                eof = neof;
+            }
+        }
+        HIP_OK(hipStreamSynchronize(ctx->stream));
     }
+
+    // the finished streams as a read library; the mapping view is kept when it is `separate`
+    void finish(Library &lib, bool separate, mcaat_reads *r) {
+        r->ctx = ctx;
+        r->n_reads = lib.n_reads;
+        r->n_bases = lib.n_bases;
+        r->n_words = (lib.n_bases + 31) / 32;
+        r->fixed_len = 0;
+        if (lib.n_reads > 0) {
+            uint64_t L = 0;
+            HIP_OK(hipMemcpy(&L, lib.offsets.p + 1, 8, hipMemcpyDeviceToHost));
+            HIP_OK(hipMemsetAsync(meta.p, 0, 4, ctx->stream));
+            launch_at(ctx->stream, dim3(grid_for(lib.n_reads + 1, kBlock)), dim3(kBlock), k_fq_fixed_len, lib.offsets.p,
+                      lib.n_reads, L, meta.p);
+            HIP_OK(hipMemcpyAsync(hmeta, meta.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+            HIP_OK(hipStreamSynchronize(ctx->stream));
+            if (!hmeta[0] && L > 0) r->fixed_len = L;
+        }
+        r->packed = std::move(lib.packed);
+        r->offsets = std::move(lib.offsets);
+        r->n_records = lib.n_rec;
+        r->file_records = lib.file_records;
+        r->has_records = separate;
+        if (r->has_records) {
+            r->rec_packed = std::move(lib.qpacked);
+            r->rec_offsets = std::move(lib.qoffsets);
+        }
+    }
+};
+
+}  // namespace
+
+// All inputs are FASTQ (checked by the caller). Files are concatenated; records of files
+// after the first are reversed and complemented in the mapping view (paired-end R2).
+void ingest_fastq(mcaat_ctx *ctx, const char *const *files, int n_files, mcaat_reads *r,
+                  const std::vector<std::pair<uint64_t, uint64_t>> *ranges) {
+    // plain files of well-formed upper-case ACGT records: packed by host threads (PCIe carries
+    // 2 bits per base); any other input falls through to the text parser below
+    if (fastq_hostpack(ctx, files, n_files, ranges, r)) return;
+    Library lib(ctx, files, n_files, ranges);
+    ChunkIo io(ctx);
+    hipStream_t st = ctx->stream;
+    uint32_t *const hmeta = io.hmeta;
+    DevBuf<uint32_t> sbeg, slen, nbase, nrun, boff, roff, qoff;
+    uint32_t flags_all = 0;
+    uint32_t nrec = 0;  // records of the chunk at hand
+
+    // records are 4 lines: the bytes after the last complete record carry over
+    auto consume = [&](int fi, int, size_t, uint32_t NL, bool eof) -> size_t {
+        nrec = NL / 4;
+        if (eof && NL % 4)
+            throw FormatError(std::string("not 4-line FASTQ (truncated record, blank or wrapped line): ") + files[fi]);
+        if (!nrec) return 0;
+        HIP_OK(hipMemcpyAsync(hmeta, io.nl.p + 4 * (uint64_t)nrec - 1, 4, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        return (size_t)hmeta[0] + 1;
+    };
+    auto parse = [&](int fi, int cur, size_t consumed) {
+        if (!nrec) return;
+        KernelTimer kt(ctx, "fq_records", (double)consumed + 16.0 * nrec);
+        if (sbeg.n < (uint64_t)nrec + 1) {
+            const uint64_t m = std::max<uint64_t>((uint64_t)nrec + 1, io.cap / 64);
+            for (auto *b : {&sbeg, &slen, &nbase, &nrun, &boff, &roff, &qoff}) b->alloc(m);
+        }
+        HIP_OK(hipMemsetAsync(io.meta.p, 0, 4, st));
+        for (auto *b : {&nbase, &nrun, &slen}) HIP_OK(hipMemsetAsync(b->p + nrec, 0, 4, st));
+        launch_at(st, dim3(grid_for(nrec, kBlock)), dim3(kBlock), k_fq_records, io.dbufs[cur].p, io.nl.p, nrec, sbeg.p,
+                  slen.p, nbase.p, nrun.p, io.meta.p);
+        scan_u32(ctx, nbase.p, boff.p, (uint64_t)nrec + 1, io.tmp);
+        scan_u32(ctx, nrun.p, roff.p, (uint64_t)nrec + 1, io.tmp);
+        scan_u32(ctx, slen.p, qoff.p, (uint64_t)nrec + 1, io.tmp);
+        HIP_OK(hipMemcpyAsync(hmeta + 0, boff.p + nrec, 4, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(hmeta + 1, roff.p + nrec, 4, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(hmeta + 2, qoff.p + nrec, 4, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(hmeta + 3, io.meta.p, 4, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        kt.stop();
+        const uint32_t cb = hmeta[0], cr = hmeta[1], cq = hmeta[2], fl = hmeta[3];
+        if (fl & kBadHeader) throw FormatError(std::string("not 4-line FASTQ (header or '+' line): ") + files[fi]);
+        flags_all |= fl;
+        if (fi > 0) flags_all |= kDiffer;  // second file: reverse-complemented records
+        lib.reserve(ctx, cb, cr, cq, nrec);
+        KernelTimer ke(ctx, "fq_emit", (double)consumed + 0.5 * (double)(cb + cq) + 8.0 * (cr + nrec));
+        launch_at(st, dim3(grid_for(nrec, kBlock)), dim3(kBlock), k_fq_emit, io.dbufs[cur].p, nrec, sbeg.p, slen.p, boff.p,
+                  roff.p, qoff.p, lib.n_bases, lib.n_reads, lib.q_bases, lib.n_rec, fi > 0 ? 1 : 0, lib.packed.p,
+                  lib.offsets.p, lib.qpacked.p, lib.qoffsets.p);
+        ke.stop();
+        lib.n_bases += cb;
+        lib.n_reads += cr;
+        lib.q_bases += cq;
+        lib.n_rec += nrec;
+    };
+    io.run("FASTQ", "fq_parse", true, files, n_files, ranges, lib.n_rec, lib.file_records, consume, parse);
+    io.finish(lib, (flags_all & kDiffer) != 0, r);
+}
+
+// All inputs are FASTA (checked by the caller): records of a '>' header line and any number of
+// sequence lines, read as the host kseq-style reader reads them (capi.hip read_fastx_host).
+// Files are concatenated; records of files after the first are reversed and complemented, over
+// the whole concatenated record, in the mapping view. A chunk is consumed up to the start of
+// its last header line (the record that header opens may continue in the next chunk), so a
+// chunk always begins at a header and no read crosses a chunk. A line that starts with '@' or
+// '+' outside a header is FASTQ grammar under kseq: FormatError, and the caller reads the input
+// again on the host, as it does for a record above the carry reserve.
+void ingest_fasta(mcaat_ctx *ctx, const char *const *files, int n_files, mcaat_reads *r,
+                  const std::vector<std::pair<uint64_t, uint64_t>> *ranges) {
+    Library lib(ctx, files, n_files, ranges);
+    ChunkIo io(ctx);
+    hipStream_t st = ctx->stream;
+    uint32_t *const hmeta = io.hmeta;
+    // per line; recx: headers before the line; prev: key of the nearest non-empty line before it
+    DevBuf<uint32_t> len, nbase, nrun, lflag, hflag, key, prev, recx, hdr, boff, roff, qoff;
+    DevBuf<uint32_t> flags(1);  // kDiffer of all chunks (k_fa_lines keeps its own in io.meta)
+    HIP_OK(hipMemsetAsync(flags.p, 0, 4, st));
+    uint32_t flags_all = 0;
+    uint32_t n_use = 0;  // lines of the chunk at hand that are consumed
+
+    auto consume = [&](int fi, int cur, size_t total, uint32_t NL, bool eof) -> size_t {
+        n_use = 0;
+        if (!NL) return 0;
+        if (len.n < (uint64_t)NL + 1) {
+            const uint64_t m = std::max<uint64_t>((uint64_t)NL + 1, io.cap / 32);
+            for (auto *b : {&len, &nbase, &nrun, &lflag, &hflag, &key, &prev, &recx, &hdr, &boff, &roff, &qoff}) b->alloc(m);
+        }
+        KernelTimer kt(ctx, "fa_lines", (double)total + 28.0 * NL);
+        HIP_OK(hipMemsetAsync(io.meta.p, 0, 12, st));
+        launch_at(st, dim3(grid_for(NL, kBlock)), dim3(kBlock), k_fa_lines, io.dbufs[cur].p, io.nl.p, NL, len.p, nbase.p,
+                  nrun.p, lflag.p, hflag.p, key.p, io.meta.p);
+        HIP_OK(hipMemcpyAsync(hmeta, io.meta.p, 12, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        kt.stop();
+        const uint32_t fl = hmeta[0], h_idx = hmeta[1], h_pos = hmeta[2];
+        if (fl & kBadHeader)
+            throw FormatError(std::string("not plain FASTA (a sequence line starts with '@' or '+'): ") + files[fi]);
+        flags_all |= fl;
+        n_use = eof ? NL : h_idx - 1;  // line 0 is a header: h_idx >= 1
+        return eof ? total : (size_t)h_pos;
+    };
+    auto parse = [&](int fi, int cur, size_t consumed) {
+        const uint32_t n = n_use;
+        if (!n) return;
+        KernelTimer kt(ctx, "fa_lines", 56.0 * n);
+        scan_u32(ctx, hflag.p, recx.p, (uint64_t)n + 1, io.tmp);
+        {
+            size_t need = 0;
+            HIP_OK(hipcub::DeviceScan::ExclusiveScan(nullptr, need, key.p, prev.p, hipcub::Max(), 0u, (size_t)n, st));
+            if (need > io.tmp.bytes()) io.tmp.alloc(need);
+            HIP_OK(hipcub::DeviceScan::ExclusiveScan(io.tmp.p, need, key.p, prev.p, hipcub::Max(), 0u, (size_t)n, st));
+        }
+        launch_at(st, dim3(grid_for((uint64_t)n + 1, kBlock)), dim3(kBlock), k_fa_link, n, prev.p, recx.p, nrun.p, lflag.p,
+                  hdr.p);
+        scan_u32(ctx, nbase.p, boff.p, (uint64_t)n + 1, io.tmp);
+        scan_u32(ctx, nrun.p, roff.p, (uint64_t)n + 1, io.tmp);
+        scan_u32(ctx, len.p, qoff.p, (uint64_t)n + 1, io.tmp);
+        HIP_OK(hipMemcpyAsync(hmeta + 0, boff.p + n, 4, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(hmeta + 1, roff.p + n, 4, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(hmeta + 2, qoff.p + n, 4, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(hmeta + 3, recx.p + n, 4, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        kt.stop();
+        const uint32_t cb = hmeta[0], cr = hmeta[1], cq = hmeta[2], nrec = hmeta[3];
+        if (fi > 0 && nrec) flags_all |= kDiffer;  // second file: reverse-complemented records
+        lib.reserve(ctx, cb, cr, cq, nrec);
+        KernelTimer ke(ctx, "fa_emit", (double)consumed + 0.5 * (double)(cb + cq) + 8.0 * (cr + nrec) + 40.0 * n);
+        launch_at(st, dim3(grid_for(n, kBlock)), dim3(kBlock), k_fa_emit, io.dbufs[cur].p, io.nl.p, n, len.p, lflag.p,
+                  recx.p, hdr.p, boff.p, roff.p, qoff.p, lib.n_bases, lib.n_reads, lib.q_bases, lib.n_rec,
+                  fi > 0 ? 1 : 0, lib.packed.p, lib.offsets.p, lib.qpacked.p, lib.qoffsets.p, flags.p);
+        ke.stop();
+        lib.n_bases += cb;
+        lib.n_reads += cr;
+        lib.q_bases += cq;
+        lib.n_rec += nrec;
+    };
+    // blank lines are transparent in FASTA, so the file's tail is not trimmed: a last line of
+    // blanks is a sequence line, as it is for kseq
+    io.run("FASTA", "fa_parse", false, files, n_files, ranges, lib.n_rec, lib.file_records, consume, parse);
+    // the end of the last read (k_fa_emit writes a read's start); any record not one ACGT run
+    HIP_OK(hipMemcpyAsync(lib.offsets.p + lib.n_reads, &lib.n_bases, 8, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(hmeta, flags.p, 4, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    flags_all |= hmeta[0];
+    io.finish(lib, (flags_all & kDiffer) != 0, r);
 }
 
 }  // namespace mcaat
@@ -732,6 +1041,33 @@ uint64_t fastq_record_start(const char *path, uint64_t pos) {
     }
     close(fd);
     return result;
+}
+
+// The file is scanned window by window from pos - 1 (so a header starting exactly at pos is
+// seen); whether a window begins a line is the last byte of the window before it.
+uint64_t fasta_record_start(const char *path, uint64_t pos) {
+    const int fd = open(path, O_RDONLY);
+    if (fd < 0) throw Error(MCAAT_E_IO, std::string("cannot open ") + path);
+    struct FdClose {
+        int fd;
+        ~FdClose() { close(fd); }
+    } closer{fd};
+    struct stat st;
+    if (fstat(fd, &st) != 0) throw Error(MCAAT_E_IO, std::string("cannot stat ") + path);
+    const uint64_t size = (uint64_t)st.st_size;
+    if (pos == 0 || pos >= size) return std::min(pos, size);
+    std::vector<uint8_t> buf(1 << 20);
+    bool line_start = false;  // pos - 1 is returned only as a '\n' before a header at pos
+    for (uint64_t at = pos - 1; at < size;) {
+        const ssize_t got = pread(fd, buf.data(), (size_t)std::min<uint64_t>(buf.size(), size - at), (off_t)at);
+        if (got < 0) throw Error(MCAAT_E_IO, std::string("read error in ") + path);
+        if (got == 0) break;
+        const size_t i = fasta_first_header(buf.data(), (size_t)got, line_start);
+        if (i < (size_t)got) return at + i;
+        line_start = buf[got - 1] == '\n';
+        at += (uint64_t)got;
+    }
+    return size;
 }
 
 }  // namespace mcaat

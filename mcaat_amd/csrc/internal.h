@@ -560,6 +560,10 @@ uint64_t graph_valid_out_ranks(const mcaat_graph *g, uint64_t *ids, uint32_t *nb
 // ranges: per file, the byte range [first, second) to read (a rank's part; null: whole files)
 void ingest_fastq(mcaat_ctx *ctx, const char *const *files, int n_files, mcaat_reads *r,
                   const std::vector<std::pair<uint64_t, uint64_t>> *ranges = nullptr);
+// FASTA(.gz/.bz2) inputs parsed on the GPU, work dealt by line (fastq_ingest.hip); FormatError
+// for an input it does not take (kseq's FASTQ grammar inside it, a record above the reserve)
+void ingest_fasta(mcaat_ctx *ctx, const char *const *files, int n_files, mcaat_reads *r,
+                  const std::vector<std::pair<uint64_t, uint64_t>> *ranges = nullptr);
 // Decompressed sequential bytes of an input file (instream.hip): gzip (zlib), bzip2 (libbz2,
 // opened at run time) or plain; concatenated members / streams are read in sequence.
 class InStream {
@@ -583,6 +587,9 @@ bool fastq_hostpack(mcaat_ctx *ctx, const char *const *files, int n_files,
                     const std::vector<std::pair<uint64_t, uint64_t>> *ranges, mcaat_reads *r);
 // first 4-line FASTQ record start at or after byte pos of a plain file (its size if none)
 uint64_t fastq_record_start(const char *path, uint64_t pos);
+// first line start at or after byte pos of a plain file whose first byte is '>' (its size if
+// none; the search itself is fasta_split.h)
+uint64_t fasta_record_start(const char *path, uint64_t pos);
 bool is_compressed_file(const char *path);  // gzip or bzip2: read whole, never split
 void write_fastq(const mcaat_reads *r, const char *path, int threads);
 void graph_save(const mcaat_graph *g, const char *path);

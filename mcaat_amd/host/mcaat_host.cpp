@@ -97,8 +97,10 @@ void SDBGBuild::BuildLib() {
         mcaat_check(mcaat_reads_from_fastx(ctx, cf.data(), (int)cf.size(), &reads_), "reading input files");
         return;
     }
-    // each rank reads its part of every file; inputs that cannot be split (FASTA, wrapped or
-    // gapped FASTQ) are read whole by rank 0, and the other ranks count nothing
+    // each rank reads its part of every file (FASTQ cut at 4-line records, FASTA at header
+    // lines); inputs that cannot be split (FASTA and FASTQ mixed, wrapped or gapped FASTQ, FASTA
+    // with a sequence line that starts with '@' or '+') are read whole by rank 0, and the other
+    // ranks count nothing
     const int rc = mcaat_reads_from_fastx_part(ctx, cf.data(), (int)cf.size(), settings.rank, settings.gpus, &reads_);
     std::vector<uint64_t> sizes(settings.gpus);
     const uint8_t ok = rc == MCAAT_OK;

@@ -478,7 +478,11 @@ class Reads:
 
     @classmethod
     def from_fastx_part(cls, ctx: Context, files: Sequence[str], part: int, n_parts: int) -> "Reads":
-        """Part `part` of n_parts of the FASTQ inputs (cut at record starts; .gz whole on part 0)."""
+        """Part `part` of n_parts of the inputs, all FASTQ or all FASTA: plain files are cut at
+        record starts (4-line FASTQ records; FASTA header lines, so a part with no header is
+        empty), .gz / .bz2 files go whole to part 0. Inputs that cannot be split (FASTA and FASTQ
+        mixed, wrapped FASTQ, a FASTA line that starts with '@' or '+', FASTA with the knob
+        fa.gpu = 0) raise McaatError: read them whole with from_fastx."""
         arr = (C.c_char_p * len(files))(*[f.encode() for f in files])
         h = C.c_void_p()
         _check(ctx._lib.mcaat_reads_from_fastx_part(ctx.h, arr, len(files), part, n_parts, C.byref(h)))
