@@ -67,6 +67,10 @@ int mcaat_reads_from_host(mcaat_ctx *ctx, const uint64_t *packed, uint64_t n_wor
  * before the first and after the last record. FASTA inputs (a '>' header line, then any number
  * of sequence lines; empty lines are transparent, a run of ACGT that continues over a line
  * break is one read) are parsed on the GPU too, by line, in the same chunks (knob fa.gpu).
+ * A block-gzip (BGZF) file of either format is inflated on the GPU as well (knob gz.gpu): the
+ * compressed bytes cross PCIe and the text lands in the buffer the parsers read; a corrupt member
+ * (CRC, ISIZE, an invalid DEFLATE stream) is MCAAT_E_IO naming the file, the member's index and
+ * its offset. Other .gz and .bz2 files are inflated by one host stream.
  * What neither parser takes is read again by the host kseq-style reader, with the same results:
  * FASTA and FASTQ mixed, wrapped or gapped FASTQ, a FASTA sequence line that starts with '@' or
  * '+' (FASTQ grammar to kseq), a record longer than the carry reserve (a quarter of the chunk,
@@ -416,6 +420,12 @@ void mcaat_reset_timing(mcaat_ctx *ctx);
  *   fa.gpu             0: FASTA always through the host kseq-style reader, and never split over
  *                      ranks (default 1: parsed on the GPU by line; kernel timers fa_parse,
  *                      fa_lines, fa_emit). The user's fallback and the tests' A/B switch
+ *   gz.gpu             0: every .gz input through one host inflate stream (zlib), block-gzip
+ *                      files too (default 1: a block-gzip file, BGZF as htslib's bgzip writes it,
+ *                      is inflated on the GPU, one wave per member, under the same FASTQ / FASTA
+ *                      parser; kernel timer bgzf_inflate, bytes = compressed in + text out).
+ *                      Single-member gzip and bzip2 keep the host stream either way, as does a
+ *                      file whose later members are not BGZF. Corrupt members are MCAAT_E_IO
  *   sdbg.adj_lds       0: adjacency by per-edge directory searches in global memory (the tests'
  *                      independent reference); 1 (default): group-aligned runs that own disjoint
  *                      in_info slot ranges, staged in LDS and written once. Any other value is

@@ -157,7 +157,14 @@ void upload_records(mcaat_ctx *ctx, const Stream &rec, mcaat_reads *r) {
 }
 
 // first non-blank byte of a (possibly compressed) file: '@' FASTQ, '>' FASTA
-int sniff_format(const char *path) {
+int sniff_format(const mcaat_ctx *ctx, const char *path) {
+    // a block-gzip file that the device will inflate (gz.gpu): only the members up to the first
+    // solid byte are inflated, so damage further on is met by whoever reads the file, who can
+    // say where it is. With gz.gpu = 0 the host stream sniffs, as it reads
+    if (knob(ctx, "gz.gpu", 1) != 0 && is_compressed_file(path) && is_bgzf_file(path)) {
+        const int c = bgzf_sniff(path);
+        if (c != -2) return c;
+    }
     InStream f(path);
     uint8_t buf[4096];
     for (;;) {
@@ -416,6 +423,7 @@ void mcaat_finalize(mcaat_ctx *ctx) {
     for (hipEvent_t e : ctx->events) (void)hipEventDestroy(e);
     if (ctx->bounce) (void)hipHostFree(ctx->bounce);
     if (ctx->pack_pinned) (void)hipHostFree(ctx->pack_pinned);
+    if (ctx->bgzf_pinned) (void)hipHostFree(ctx->bgzf_pinned);
     if (ctx->side) (void)hipStreamDestroy(ctx->side);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
@@ -459,7 +467,7 @@ int mcaat_reads_from_fastx(mcaat_ctx *ctx, const char *const *files, int n_files
         // place in the file order (a second file's records are reverse-complemented)
         int n_fastq = 0, n_fasta = 0;
         for (int i = 0; i < n_files; ++i) {
-            const int c = sniff_format(files[i]);
+            const int c = sniff_format(ctx, files[i]);
             if (c == '@') ++n_fastq;
             else if (c == '>') ++n_fasta;
             else if (c != -1) throw Error(MCAAT_E_IO, std::string("not FASTA/FASTQ: ") + files[i]);
@@ -1117,7 +1125,7 @@ int mcaat_set_knob(mcaat_ctx *ctx, const char *name, int64_t value) {
         "fq.hostpack",     "nc.big_table", "cf.fused_init", "cf.dls_lanes", "dist.oriented",
         "sort.small_mid", "sort.small_limit", "cf.dls_host",
         "dist.desc",      "cf.compact",         "cf.fresh",   "nc.split_first", "nc.split_max", "cf.dls_budget", "nc.grow_early",
-        "nc.free_sync", "dist.shard_cf", "dist.ruler_mask", "dist.adj_chunk", "dist.dir_edges", "nc.ahead", "dist.adj_ranges", "dist.win_ranges", "cf.dls_lds", "cf.dls_lds_cap", "dist.segs_at_one", "nc.a_mini", "nc.a_adapt", "nc.a_stats", "dist.bfs_sync", "cf.compact_pct", "dist.bfs_block", "dist.bfs_frontier", "dist.res_fixed", "dist.res_batch", "dist.res_block_mb", "dist.walk_block", "dist.walk_batch", "dist.grid_blocks", "dist.preagg", "fa.gpu"};
+        "nc.free_sync", "dist.shard_cf", "dist.ruler_mask", "dist.adj_chunk", "dist.dir_edges", "nc.ahead", "dist.adj_ranges", "dist.win_ranges", "cf.dls_lds", "cf.dls_lds_cap", "dist.segs_at_one", "nc.a_mini", "nc.a_adapt", "nc.a_stats", "dist.bfs_sync", "cf.compact_pct", "dist.bfs_block", "dist.bfs_frontier", "dist.res_fixed", "dist.res_batch", "dist.res_block_mb", "dist.walk_block", "dist.walk_batch", "dist.grid_blocks", "dist.preagg", "fa.gpu", "gz.gpu"};
     return guarded([&] {
         require(ctx && name, "null argument");
         bool ok = false;
@@ -1260,7 +1268,7 @@ int mcaat_reads_from_fastx_part(mcaat_ctx *ctx, const char *const *files, int n_
         // all FASTQ or all FASTA (empty files go with either); a file is cut at record starts
         int n_fastq = 0, n_fasta = 0;
         for (int i = 0; i < n_files; ++i) {
-            const int c = sniff_format(files[i]);
+            const int c = sniff_format(ctx, files[i]);
             n_fastq += c == '@';
             n_fasta += c == '>';
         }

@@ -440,15 +440,18 @@ void grow(mcaat_ctx *ctx, DevBuf<uint64_t> &b, uint64_t used, uint64_t need) {
 // for plain files (one thread copies page-cache data at ~13 GB/s; eight reach ~38 GB/s end to end).
 struct Source {
     std::unique_ptr<InStream> z;  // gzip / bzip2
+    std::unique_ptr<BgzfReader> bgzf;  // block gzip: whole members, inflated on the device
     int fd = -1;
     uint64_t off = 0;
     const char *path;
     uint64_t end = ~0ULL;  // plain files: read [off, end) only (a rank's part of the file)
     // [begin, end) of a plain file; a compressed file is read whole (begin = 0, end = ~0)
-    explicit Source(const char *p, uint64_t begin = 0, uint64_t end_ = ~0ULL) : off(begin), path(p), end(end_) {
+    explicit Source(const char *p, uint64_t begin = 0, uint64_t end_ = ~0ULL, bool device_inflate = false)
+        : off(begin), path(p), end(end_) {
         if (is_compressed_file(p)) {
             if (begin != 0 || end_ != ~0ULL) throw Error(MCAAT_E_INVALID, "a compressed input cannot be split");
-            z.reset(new InStream(p));
+            if (device_inflate && is_bgzf_file(p)) bgzf.reset(new BgzfReader(p));
+            else z.reset(new InStream(p));
             return;
         }
         fd = open(p, O_RDONLY);
@@ -585,8 +588,31 @@ struct ChunkIo {
     DevBuf<uint8_t> tmp;
     uint32_t *hmeta = nullptr;  // pinned words for the counters read back per chunk
 
-    explicit ChunkIo(mcaat_ctx *c)
-        : ctx(c), CH(fastq_chunk_bytes()), R(std::max<size_t>(CH / 4, 4096)), cap(R + CH + 2 * kSeg) {
+    // ---- block-gzip files (device_inflate): the reader fills hb[x] + R with whole members, they
+    // are staged in zbuf[x] and k_bgzf_inflate writes their text behind the carry in dbufs[x].
+    // A file's first member may begin with blank bytes that are not part of the chunk: it is
+    // inflated up to kFront bytes in front of the text, so a chunk's text begins kFront bytes
+    // into its buffer (uploaded text too: one layout).
+    static constexpr size_t kFront = 65536;
+    static constexpr uint32_t kMaxMembers = 1u << 16;  // per chunk: 1 MiB of table
+    const bool device_inflate;                         // knob gz.gpu
+    DevBuf<uint8_t> zbuf[2];
+    DevBuf<BgzfMember> dtab[2];
+    DevBuf<uint32_t> dstat[2];  // [0] smallest failing member, [1] text length at the end of the file, [2 + i] status
+    BgzfMember *htab[2] = {nullptr, nullptr};  // pinned (ctx->bgzf_pinned)
+    uint32_t *hstat = nullptr;                 // pinned (the same block): words [0], [1] of dstat[x] at hstat + 2 x
+    std::vector<uint32_t> mstart[2];           // a member's offset in the chunk's compressed bytes
+    struct Inflate {                           // the inflate of chunk x, queued and not yet waited for
+        bool active = false, eof = false;
+        std::unique_ptr<KernelTimer> kt;
+        BgzfChunk ck;
+        uint32_t dropped = 0;  // blank leading members the host inflated itself
+    } inflate[2];
+    uint8_t *text(int x) const { return dbufs[x].p + kFront; }
+
+    explicit ChunkIo(mcaat_ctx *c, bool device_inflate_ = false)
+        : ctx(c), CH(fastq_chunk_bytes()), R(std::max<size_t>(CH / 4, 4096)), cap(R + CH + 2 * kSeg),
+          device_inflate(device_inflate_) {
         if (ctx->pinned_bytes < cap) {
             for (auto *&p : ctx->pinned) {
                 if (p) (void)hipHostFree(p);
@@ -598,8 +624,8 @@ struct ChunkIo {
         }
         hb[0] = ctx->pinned[0];
         hb[1] = ctx->pinned[1];
-        dbufs[0].alloc(cap);
-        dbufs[1].alloc(cap);
+        dbufs[0].alloc(kFront + cap);
+        dbufs[1].alloc(kFront + cap);
         for (auto &e : cs.done) HIP_OK(hipEventRecord(e, ctx->stream));
         const uint64_t max_seg = cap / kSeg + 1;
         cnt.alloc(max_seg + 1);
@@ -610,10 +636,109 @@ struct ChunkIo {
         HIP_OK(hipHostMalloc((void **)&hmeta, 64, hipHostMallocDefault));
     }
     ~ChunkIo() {
+        (void)hipStreamSynchronize(cs.s);  // an error unwinding: the staging buffers may be in use
         if (hmeta) (void)hipHostFree(hmeta);
     }
     ChunkIo(const ChunkIo &) = delete;
     ChunkIo &operator=(const ChunkIo &) = delete;
+
+    // the staging buffers and tables of the device inflate, at the first block-gzip file. The
+    // pinned tables and status words are one block kept in the context between calls (pinning
+    // costs more than a small file's ingest); the device buffers come from the caching arena
+    void ensure_inflate() {
+        if (hstat) return;
+        const size_t tab_bytes = sizeof(BgzfMember) * kMaxMembers;
+        if (!ctx->bgzf_pinned) HIP_OK(hipHostMalloc((void **)&ctx->bgzf_pinned, 2 * tab_bytes + 64, hipHostMallocDefault));
+        hstat = (uint32_t *)(ctx->bgzf_pinned + 2 * tab_bytes);
+        for (int x = 0; x < 2; ++x) {
+            htab[x] = (BgzfMember *)(ctx->bgzf_pinned + x * tab_bytes);
+            mstart[x].resize(kMaxMembers);
+            zbuf[x].alloc(CH + 64);
+            dtab[x].alloc(kMaxMembers);
+            dstat[x].alloc(kMaxMembers + 2);
+        }
+    }
+
+    // Chunk x of a block-gzip file: the carry (carry_x bytes at carry_src, on the device) copied
+    // to the front of the text, the members ck describes (compressed bytes in hb[x] + R, table
+    // in htab[x]) staged and inflated behind it, all on the copy stream; cs.ev[x] marks
+    // completion. The text is what the host path would have uploaded: leading blank bytes of
+    // the file are left out (while `leading`, the host inflates members until it meets a solid
+    // byte; wholly blank ones are dropped from the table, the next one is inflated that far in
+    // front of the text), the file's tail is finished by k_bgzf_tail. total_x is final unless
+    // the chunk ends the file: wait_inflate() then has the length.
+    void prepare_inflate(int x, size_t carry_x, const uint8_t *carry_src, const BgzfChunk &ck, bool &leading,
+                         bool trim_tail, size_t &total_x) {
+        const uint8_t *zsrc = hb[x] + R;
+        BgzfMember *tab = htab[x];
+        uint32_t n = ck.n_members, lead = 0, dropped = 0;
+        if (leading) {  // no solid byte of the file seen yet (a chunk of blank members: still none)
+            std::vector<uint8_t> t;
+            for (uint32_t i = 0; i < n && leading; ++i) {
+                if (!bgzf_host_inflate(zsrc, tab[i], t)) break;  // corrupt: the kernel reports it
+                uint32_t k = 0;
+                while (k < tab[i].olen && is_space(t[k])) ++k;
+                lead += k;
+                if (k < tab[i].olen) leading = false;
+                else dropped = i + 1;
+            }
+            if (dropped) {
+                memmove(tab, tab + dropped, sizeof(BgzfMember) * (n - dropped));
+                memmove(mstart[x].data(), mstart[x].data() + dropped, 4 * (size_t)(n - dropped));
+                n -= dropped;
+            }
+        }
+        total_x = carry_x + ck.text - lead;
+        Inflate &in = inflate[x];
+        in.active = true;
+        in.eof = ck.eof;
+        in.ck = ck;
+        in.ck.n_members = n;
+        in.dropped = dropped;
+        // dbufs[x] is free once the kernels of the chunk it held last have run
+        HIP_OK(hipStreamWaitEvent(cs.s, cs.done[x], 0));
+        if (carry_x) HIP_OK(hipMemcpyAsync(text(x), carry_src, carry_x, hipMemcpyDeviceToDevice, cs.s));
+        HIP_OK(hipMemsetAsync(dstat[x].p, 0xFF, 8, cs.s));
+        if (n) {
+            HIP_OK(hipMemcpyAsync(zbuf[x].p, zsrc, ck.zbytes, hipMemcpyHostToDevice, cs.s));
+            HIP_OK(hipMemcpyAsync(dtab[x].p, tab, sizeof(BgzfMember) * n, hipMemcpyHostToDevice, cs.s));
+            in.kt.reset(new KernelTimer(ctx, "bgzf_inflate", (double)ck.zbytes + (double)ck.text, cs.s));
+            // member i's text at text + carry + ooff - lead (ooff counts from the chunk's first member)
+            bgzf_inflate_launch(cs.s, zbuf[x].p, dtab[x].p, n, text(x) + carry_x - lead, dstat[x].p + 2, dstat[x].p);
+            in.kt->mark();
+        }
+        if (ck.eof) {
+            bgzf_tail_launch(cs.s, text(x), (uint32_t)total_x, trim_tail, dstat[x].p + 1);
+        } else if (total_x) {
+            const size_t padded = (total_x + kSeg - 1) / kSeg * kSeg + kSeg;
+            HIP_OK(hipMemsetAsync(text(x) + total_x, 0, padded - total_x, cs.s));
+        }
+        HIP_OK(hipMemcpyAsync(hstat + 2 * x, dstat[x].p, 8, hipMemcpyDeviceToHost, cs.s));
+        HIP_OK(hipEventRecord(cs.ev[x], cs.s));
+    }
+
+    // waits for the inflate of chunk x; corrupt data is an error that names the member. Returns
+    // the chunk's text length (the tail kernel's at the end of the file)
+    size_t wait_inflate(int x, size_t total, const char *path) {
+        Inflate &in = inflate[x];
+        if (!in.active) return total;
+        in.active = false;
+        HIP_OK(hipEventSynchronize(cs.ev[x]));
+        if (in.kt) {
+            in.kt->finish();
+            in.kt.reset();
+        }
+        const uint32_t bad = hstat[2 * x];
+        if (bad != ~0u) {
+            uint32_t st = 0;
+            if (bad < in.ck.n_members) HIP_OK(hipMemcpy(&st, dstat[x].p + 2 + bad, 4, hipMemcpyDeviceToHost));
+            throw Error(MCAAT_E_IO, std::string("corrupt BGZF data in ") + path + ": member " +
+                                        std::to_string(in.ck.first_index + in.dropped + bad) + " at offset " +
+                                        std::to_string(in.ck.file_off + (bad < in.ck.n_members ? mstart[x][bad] : 0)) +
+                                        ": " + bgzf_status_text(st));
+        }
+        return in.eof ? (size_t)hstat[2 * x + 1] : total;
+    }
 
     // chunk x: host bytes [start, start+total) of hb[x] (carry + new data; blank bytes trimmed
     // at the file's start and, with trim_tail, at its end; a last line without its newline gets
@@ -633,8 +758,8 @@ struct ChunkIo {
             const size_t padded = (total_x + kSeg - 1) / kSeg * kSeg + kSeg;
             // dbufs[x] is free once the kernels of the chunk it held last have run
             HIP_OK(hipStreamWaitEvent(cs.s, cs.done[x], 0));
-            HIP_OK(hipMemcpyAsync(dbufs[x].p, start_x, total_x, hipMemcpyHostToDevice, cs.s));
-            HIP_OK(hipMemsetAsync(dbufs[x].p + total_x, 0, padded - total_x, cs.s));
+            HIP_OK(hipMemcpyAsync(text(x), start_x, total_x, hipMemcpyHostToDevice, cs.s));
+            HIP_OK(hipMemsetAsync(text(x) + total_x, 0, padded - total_x, cs.s));
             HIP_OK(hipEventRecord(cs.ev[x], cs.s));
         }
     }
@@ -647,9 +772,9 @@ struct ChunkIo {
         HIP_OK(hipStreamWaitEvent(ctx->stream, cs.ev[x], 0));
         KernelTimer kt(ctx, timer, 2.0 * (double)total);
         HIP_OK(hipMemsetAsync(cnt.p + nseg, 0, 4, ctx->stream));
-        launch_at(ctx->stream, dim3(grid_for(nseg, kBlock)), dim3(kBlock), k_fq_nlcount, dbufs[x].p, nseg, cnt.p);
+        launch_at(ctx->stream, dim3(grid_for(nseg, kBlock)), dim3(kBlock), k_fq_nlcount, text(x), nseg, cnt.p);
         scan_u32(ctx, cnt.p, first.p, (uint64_t)nseg + 1, tmp);
-        launch_at(ctx->stream, dim3(grid_for(nseg, kBlock)), dim3(kBlock), k_fq_nlpos, dbufs[x].p, nseg, first.p, nl.p);
+        launch_at(ctx->stream, dim3(grid_for(nseg, kBlock)), dim3(kBlock), k_fq_nlpos, text(x), nseg, first.p, nl.p);
         HIP_OK(hipMemcpyAsync(hmeta, first.p + nseg, 4, hipMemcpyDeviceToHost, ctx->stream));
         HIP_OK(hipStreamSynchronize(ctx->stream));
         kt.stop();
@@ -673,7 +798,12 @@ struct ChunkIo {
                 ~FileDone() { v.push_back(n - before); }
             } file_done{file_records, n_rec, rec_before};
             if (ranges && (*ranges)[fi].first >= (*ranges)[fi].second) continue;  // no part of this file
-            Source src(files[fi], ranges ? (*ranges)[fi].first : 0, ranges ? (*ranges)[fi].second : ~0ULL);
+            Source src(files[fi], ranges ? (*ranges)[fi].first : 0, ranges ? (*ranges)[fi].second : ~0ULL,
+                       device_inflate);
+            if (src.bgzf) {
+                run_bgzf(what, nl_timer, trim_tail, files[fi], fi, src, consume, parse);
+                continue;
+            }
             int cur = 0;
             size_t n = src.read(hb[cur] + R, chunk);
             bool eof = n < chunk;
@@ -720,6 +850,50 @@ struct ChunkIo {
         HIP_OK(hipStreamSynchronize(ctx->stream));
     }
 
+    // One block-gzip file, chunk by chunk: run()'s loop with the text inflated on the device. The
+    // carry goes from chunk to chunk on the device (after this chunk's newline pass, before the
+    // next chunk's inflate, both on the copy stream), and the end of the file is the member
+    // walk's flag: chunks of whole members have no fixed size.
+    template <class Consume, class Parse>
+    void run_bgzf(const char *what, const char *nl_timer, bool trim_tail, const char *path, int fi, Source &src,
+                  Consume &consume, Parse &parse) {
+        ensure_inflate();
+        BgzfReader &rd = *src.bgzf;
+        auto fill = [this, &rd](int x) { return rd.fill(hb[x] + R, CH, htab[x], mstart[x].data(), kMaxMembers); };
+        int cur = 0;
+        const BgzfChunk ck = fill(cur);
+        bool eof = ck.eof;
+        size_t total = 0;
+        bool leading = true;  // the file's leading blank bytes are not yet behind us
+        prepare_inflate(cur, 0, nullptr, ck, leading, trim_tail, total);
+        std::future<BgzfChunk> next;
+        if (!eof) next = std::async(std::launch::async, fill, cur ^ 1);
+        for (;;) {
+            total = wait_inflate(cur, total, path);
+            const uint32_t NL = newlines(cur, total, nl_timer);
+            const size_t consumed = consume(fi, cur, total, NL, eof);
+            if (!eof && total - consumed > R)
+                throw FormatError(std::string(what) + " record longer than the chunk reserve (" + std::to_string(R) +
+                                  " bytes): " + path);
+            const bool have_next = !eof;
+            size_t ntotal = 0;
+            bool neof = true;
+            if (have_next) {
+                const BgzfChunk nk = next.get();
+                neof = nk.eof;
+                prepare_inflate(cur ^ 1, total - consumed, text(cur) + consumed, nk, leading, trim_tail, ntotal);
+                // this chunk's compressed bytes and table are on the device: its host buffers are free
+                if (!neof) next = std::async(std::launch::async, fill, cur);
+            }
+            parse(fi, cur, consumed);
+            HIP_OK(hipEventRecord(cs.done[cur], ctx->stream));
+            if (!have_next) break;
+            cur ^= 1;
+            total = ntotal;
+            eof = neof;
+        }
+    }
+
     // the finished streams as a read library; the mapping view is kept when it is `separate`
     void finish(Library &lib, bool separate, mcaat_reads *r) {
         r->ctx = ctx;
@@ -753,13 +927,11 @@ struct ChunkIo {
 
 // All inputs are FASTQ (checked by the caller). Files are concatenated; records of files
 // after the first are reversed and complemented in the mapping view (paired-end R2).
-void ingest_fastq(mcaat_ctx *ctx, const char *const *files, int n_files, mcaat_reads *r,
-                  const std::vector<std::pair<uint64_t, uint64_t>> *ranges) {
-    // plain files of well-formed upper-case ACGT records: packed by host threads (PCIe carries
-    // 2 bits per base); any other input falls through to the text parser below
-    if (fastq_hostpack(ctx, files, n_files, ranges, r)) return;
+namespace {
+void ingest_fastq_text(mcaat_ctx *ctx, const char *const *files, int n_files, mcaat_reads *r, const Ranges *ranges,
+                       bool device_inflate) {
     Library lib(ctx, files, n_files, ranges);
-    ChunkIo io(ctx);
+    ChunkIo io(ctx, device_inflate);
     hipStream_t st = ctx->stream;
     uint32_t *const hmeta = io.hmeta;
     DevBuf<uint32_t> sbeg, slen, nbase, nrun, boff, roff, qoff;
@@ -785,7 +957,7 @@ void ingest_fastq(mcaat_ctx *ctx, const char *const *files, int n_files, mcaat_r
         }
         HIP_OK(hipMemsetAsync(io.meta.p, 0, 4, st));
         for (auto *b : {&nbase, &nrun, &slen}) HIP_OK(hipMemsetAsync(b->p + nrec, 0, 4, st));
-        launch_at(st, dim3(grid_for(nrec, kBlock)), dim3(kBlock), k_fq_records, io.dbufs[cur].p, io.nl.p, nrec, sbeg.p,
+        launch_at(st, dim3(grid_for(nrec, kBlock)), dim3(kBlock), k_fq_records, io.text(cur), io.nl.p, nrec, sbeg.p,
                   slen.p, nbase.p, nrun.p, io.meta.p);
         scan_u32(ctx, nbase.p, boff.p, (uint64_t)nrec + 1, io.tmp);
         scan_u32(ctx, nrun.p, roff.p, (uint64_t)nrec + 1, io.tmp);
@@ -802,7 +974,7 @@ void ingest_fastq(mcaat_ctx *ctx, const char *const *files, int n_files, mcaat_r
         if (fi > 0) flags_all |= kDiffer;  // second file: reverse-complemented records
         lib.reserve(ctx, cb, cr, cq, nrec);
         KernelTimer ke(ctx, "fq_emit", (double)consumed + 0.5 * (double)(cb + cq) + 8.0 * (cr + nrec));
-        launch_at(st, dim3(grid_for(nrec, kBlock)), dim3(kBlock), k_fq_emit, io.dbufs[cur].p, nrec, sbeg.p, slen.p, boff.p,
+        launch_at(st, dim3(grid_for(nrec, kBlock)), dim3(kBlock), k_fq_emit, io.text(cur), nrec, sbeg.p, slen.p, boff.p,
                   roff.p, qoff.p, lib.n_bases, lib.n_reads, lib.q_bases, lib.n_rec, fi > 0 ? 1 : 0, lib.packed.p,
                   lib.offsets.p, lib.qpacked.p, lib.qoffsets.p);
         ke.stop();
@@ -814,6 +986,25 @@ void ingest_fastq(mcaat_ctx *ctx, const char *const *files, int n_files, mcaat_r
     io.run("FASTQ", "fq_parse", true, files, n_files, ranges, lib.n_rec, lib.file_records, consume, parse);
     io.finish(lib, (flags_all & kDiffer) != 0, r);
 }
+}  // namespace
+
+void ingest_fastq(mcaat_ctx *ctx, const char *const *files, int n_files, mcaat_reads *r,
+                  const std::vector<std::pair<uint64_t, uint64_t>> *ranges) {
+    // plain files of well-formed upper-case ACGT records: packed by host threads (PCIe carries
+    // 2 bits per base); any other input falls through to the text parser
+    if (fastq_hostpack(ctx, files, n_files, ranges, r)) return;
+    // block-gzip files are inflated on the device (knob gz.gpu). When the member walk declines
+    // one (BgzfDecline), this ingest starts again from the first file with the host inflate
+    // stream under the same parser: nothing of the first attempt is kept, r is written last.
+    if (knob(ctx, "gz.gpu", 1) != 0) {
+        try {
+            ingest_fastq_text(ctx, files, n_files, r, ranges, true);
+            return;
+        } catch (const BgzfDecline &) {
+        }
+    }
+    ingest_fastq_text(ctx, files, n_files, r, ranges, false);
+}
 
 // All inputs are FASTA (checked by the caller): records of a '>' header line and any number of
 // sequence lines, read as the host kseq-style reader reads them (capi.hip read_fastx_host).
@@ -823,10 +1014,11 @@ void ingest_fastq(mcaat_ctx *ctx, const char *const *files, int n_files, mcaat_r
 // chunk always begins at a header and no read crosses a chunk. A line that starts with '@' or
 // '+' outside a header is FASTQ grammar under kseq: FormatError, and the caller reads the input
 // again on the host, as it does for a record above the carry reserve.
-void ingest_fasta(mcaat_ctx *ctx, const char *const *files, int n_files, mcaat_reads *r,
-                  const std::vector<std::pair<uint64_t, uint64_t>> *ranges) {
+namespace {
+void ingest_fasta_text(mcaat_ctx *ctx, const char *const *files, int n_files, mcaat_reads *r, const Ranges *ranges,
+                       bool device_inflate) {
     Library lib(ctx, files, n_files, ranges);
-    ChunkIo io(ctx);
+    ChunkIo io(ctx, device_inflate);
     hipStream_t st = ctx->stream;
     uint32_t *const hmeta = io.hmeta;
     // per line; recx: headers before the line; prev: key of the nearest non-empty line before it
@@ -845,7 +1037,7 @@ void ingest_fasta(mcaat_ctx *ctx, const char *const *files, int n_files, mcaat_r
         }
         KernelTimer kt(ctx, "fa_lines", (double)total + 28.0 * NL);
         HIP_OK(hipMemsetAsync(io.meta.p, 0, 12, st));
-        launch_at(st, dim3(grid_for(NL, kBlock)), dim3(kBlock), k_fa_lines, io.dbufs[cur].p, io.nl.p, NL, len.p, nbase.p,
+        launch_at(st, dim3(grid_for(NL, kBlock)), dim3(kBlock), k_fa_lines, io.text(cur), io.nl.p, NL, len.p, nbase.p,
                   nrun.p, lflag.p, hflag.p, key.p, io.meta.p);
         HIP_OK(hipMemcpyAsync(hmeta, io.meta.p, 12, hipMemcpyDeviceToHost, st));
         HIP_OK(hipStreamSynchronize(st));
@@ -883,7 +1075,7 @@ void ingest_fasta(mcaat_ctx *ctx, const char *const *files, int n_files, mcaat_r
         if (fi > 0 && nrec) flags_all |= kDiffer;  // second file: reverse-complemented records
         lib.reserve(ctx, cb, cr, cq, nrec);
         KernelTimer ke(ctx, "fa_emit", (double)consumed + 0.5 * (double)(cb + cq) + 8.0 * (cr + nrec) + 40.0 * n);
-        launch_at(st, dim3(grid_for(n, kBlock)), dim3(kBlock), k_fa_emit, io.dbufs[cur].p, io.nl.p, n, len.p, lflag.p,
+        launch_at(st, dim3(grid_for(n, kBlock)), dim3(kBlock), k_fa_emit, io.text(cur), io.nl.p, n, len.p, lflag.p,
                   recx.p, hdr.p, boff.p, roff.p, qoff.p, lib.n_bases, lib.n_reads, lib.q_bases, lib.n_rec,
                   fi > 0 ? 1 : 0, lib.packed.p, lib.offsets.p, lib.qpacked.p, lib.qoffsets.p, flags.p);
         ke.stop();
@@ -901,6 +1093,20 @@ void ingest_fasta(mcaat_ctx *ctx, const char *const *files, int n_files, mcaat_r
     HIP_OK(hipStreamSynchronize(st));
     flags_all |= hmeta[0];
     io.finish(lib, (flags_all & kDiffer) != 0, r);
+}
+}  // namespace
+
+void ingest_fasta(mcaat_ctx *ctx, const char *const *files, int n_files, mcaat_reads *r,
+                  const std::vector<std::pair<uint64_t, uint64_t>> *ranges) {
+    // block-gzip files on the device, the host inflate stream when the walk declines: as ingest_fastq
+    if (knob(ctx, "gz.gpu", 1) != 0) {
+        try {
+            ingest_fasta_text(ctx, files, n_files, r, ranges, true);
+            return;
+        } catch (const BgzfDecline &) {
+        }
+    }
+    ingest_fasta_text(ctx, files, n_files, r, ranges, false);
 }
 
 }  // namespace mcaat

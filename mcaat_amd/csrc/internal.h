@@ -175,6 +175,9 @@ struct mcaat_ctx {
     // pinned staging of the host FASTQ packer (two buffers per packing thread), kept
     uint8_t *pack_pinned = nullptr;
     size_t pack_pinned_bytes = 0;
+    // pinned member tables and status words of the device BGZF inflate (fastq_ingest.hip
+    // ChunkIo::ensure_inflate; a fixed size), kept between calls like the chunks above
+    uint8_t *bgzf_pinned = nullptr;
     // mcaat_count_ahead: the next host-packed FASTQ read runs node_counter's pass A for this k
     // on its parts as they land (0: off; one read takes it)
     int ahead_k = 0;
@@ -591,6 +594,57 @@ uint64_t fastq_record_start(const char *path, uint64_t pos);
 // none; the search itself is fasta_split.h)
 uint64_t fasta_record_start(const char *path, uint64_t pos);
 bool is_compressed_file(const char *path);  // gzip or bzip2: read whole, never split
+// ---- block-gzip (BGZF) input inflated on the device (bgzf_inflate.hip)
+// one gzip member of a chunk: its DEFLATE stream in the staged compressed bytes (the CRC-32 /
+// ISIZE trailer follows it) and where its text goes
+struct BgzfMember {
+    uint32_t zoff, zlen, ooff, olen;
+};
+// input the member walk does not take: the ingest starts again with the host inflate stream
+struct BgzfDecline : Error {
+    explicit BgzfDecline(const std::string &m) : Error(MCAAT_E_IO, m) {}
+};
+struct BgzfChunk {
+    size_t zbytes = 0;         // compressed bytes: whole consecutive members
+    size_t text = 0;           // sum of their ISIZE
+    uint32_t n_members = 0;
+    bool eof = false;          // the file's last member is in this chunk (or an earlier one)
+    uint64_t file_off = 0;     // where the chunk begins in the file
+    uint64_t first_index = 0;  // the file-wide index of its first member
+};
+// first gzip member: CM 8, FEXTRA, a 'BC' subfield of 2 bytes among the extra subfields
+bool is_bgzf_file(const char *path);
+// Sequential reader of whole members. fill(): the longest run of whole consecutive members with
+// compressed bytes <= CH, text <= CH and at most max_members members, read into dst; tab and
+// mstart (a member's offset in dst) get one entry per member. BgzfDecline for a later member
+// that is not BGZF, junk between members, a BSIZE past the end of the file, a member above CH.
+class BgzfReader {
+   public:
+    explicit BgzfReader(const char *path);
+    ~BgzfReader();
+    BgzfReader(const BgzfReader &) = delete;
+    BgzfReader &operator=(const BgzfReader &) = delete;
+    BgzfChunk fill(uint8_t *dst, size_t CH, BgzfMember *tab, uint32_t *mstart, uint32_t max_members);
+
+   private:
+    static constexpr size_t kStep = size_t(4) << 20;  // bytes per read: what a chunk reads too far is read again
+    std::string path;
+    int fd = -1;
+    uint64_t fsize = 0, off = 0, index = 0;
+};
+// first byte of the file's text that is not blank, looking no further than the member that
+// holds it (zlib on the host): -1 none, -2 not decided here (not BGZF throughout, or corrupt)
+int bgzf_sniff(const char *path);
+// one member inflated by zlib on the host (the text edges of a file); false: corrupt
+bool bgzf_host_inflate(const uint8_t *z, const BgzfMember &m, std::vector<uint8_t> &text);
+// k_bgzf_inflate on stream s: member i of tab (device) from z + zoff to out + ooff; status[i] is
+// its inflate_core.h status, first_bad[0] (preset to ~0) the smallest failing index
+void bgzf_inflate_launch(hipStream_t s, const uint8_t *z, const BgzfMember *tab, uint32_t n, uint8_t *out,
+                         uint32_t *status, uint32_t *first_bad);
+// the end of a file's text on the device: trailing blank bytes trimmed (trim), a final newline
+// and the zero padding added; out_total[0] gets the length
+void bgzf_tail_launch(hipStream_t s, uint8_t *text, uint32_t total, bool trim, uint32_t *out_total);
+const char *bgzf_status_text(uint32_t status);
 void write_fastq(const mcaat_reads *r, const char *path, int threads);
 void graph_save(const mcaat_graph *g, const char *path);
 void graph_load(mcaat_ctx *ctx, const char *path, mcaat_graph *g);
